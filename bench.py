@@ -22,10 +22,16 @@ Multi-GPU: game shards are independent (rank r owns global games
 on the data path; one RCCL all_reduce of the per-rank score sums after the
 timed loop is the score gather.
 
-Extra legs (reported beside the headline, never in `value`): config 3
-(MCS), config 4 (PUCT, PUCTCustomed), and config 5 on every rank: the
-batched tournament (league.py) -- 65 536 concurrent tournament slots per GPU
-with per-game seat draws, then the RCCL gather of the per-agent sums and
+A plain run (`--gpus N --steps K --warmup W`) sets up, warms up, times the
+K launches, writes the last timed launch's outputs when `--dump-outputs DIR`
+is given, and prints the headline line.  Everything else runs only under
+`--full`: the per-kernel HIP-event pass and the roofline built on it, the
+CPU baseline, the philox leg, and the extra legs.
+
+Extra legs (`--full`; reported beside the headline, never in `value`):
+config 3 (MCS), config 4 (PUCT, PUCTCustomed), and config 5 on every rank:
+the batched tournament (league.py) -- 65 536 concurrent tournament slots per
+GPU with per-game seat draws, then the RCCL gather of the per-agent sums and
 every game's record and the rank-0 Elo replay.
 """
 import argparse
@@ -71,6 +77,12 @@ def parse():
     ap.add_argument("--steps", type=int, default=200, help="timed launches (episodes)")
     ap.add_argument("--warmup", type=int, default=20,
                     help="untimed launches first (several twist groups: the pipeline in its steady state)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run the per-kernel timing pass (roofline), the CPU baseline, the "
+                         "philox leg and the extra legs (configs 1, 3, 4, 5, drop-in); --only / --no-* choose among them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed launches write the last one's outputs (rewards, done, actions, obs) as "
+                         "DIR/<name>.npy in float32; an array above 15 MB is cut to a fixed, seeded sample of its games")
     ap.add_argument("--games", type=int, default=65536, help="games per GPU")
     ap.add_argument("--rng", default="numpy", choices=["numpy", "philox"])
     ap.add_argument("--no-obs", action="store_true", help="do not emit observations (not the headline)")
@@ -178,13 +190,16 @@ def barrier(world):
 ENQUEUE_S = None
 
 
-def time_rollouts(env, out, steps, warmup, world, per_call=1):
+def time_rollouts(env, out, steps, warmup, world, per_call=1, kernel_pass=True, after_timed=None):
     """Warm up, then time exactly `steps` launches between barrier+sync on
     both sides (nothing else enqueued in between: per-launch timing events
-    on the stream cost the pipelined step ~30 %).  Returns (wall seconds,
-    mean per-launch ms from HIP events around each launch in a second pass of
-    the same `steps` launches, per-kernel times)."""
+    on the stream cost the pipelined step ~30 %).  `after_timed`, if given,
+    is then called with the last timed launch's outputs (views of `out`).
+    Returns (wall seconds, mean per-launch ms from HIP events around each
+    launch in a second pass of the same `steps` launches, per-kernel times);
+    without `kernel_pass` there is no second pass and both are None."""
     one = {k: v[:STEPS_PER_LAUNCH] for k, v in out.items()}  # one launch's outputs
+    last = one
     for _ in range(warmup):
         env.rollout(STEPS_PER_LAUNCH, out=one)
     torch.cuda.synchronize()
@@ -203,6 +218,13 @@ def time_rollouts(env, out, steps, warmup, world, per_call=1):
     torch.cuda.synchronize()
     barrier(world)
     t1 = time.perf_counter()
+    if after_timed is not None:
+        if per_call != 1 and steps > 0:  # the last call's last launch wrote the tail of its [10 n]-step slice
+            n = ((steps - 1) % per_call + 1) * STEPS_PER_LAUNCH
+            last = {k: v[n - STEPS_PER_LAUNCH:n] for k, v in out.items()}
+        after_timed(last)
+    if not kernel_pass:
+        return t1 - t0, None, None
     # second pass: HIP events around each launch on the launch stream, and
     # (numpy mode) inside the library around each kernel on its own stream --
     # over at least KERNEL_PASS_MIN launches (a 20-launch pass is dominated by
@@ -222,6 +244,25 @@ def time_rollouts(env, out, steps, warmup, world, per_call=1):
     play_ms, ahead_ms, dec_ms, n = env.kernel_times(with_decode=True)
     env.time_kernels(0)
     return t1 - t0, kern_ms, {"k_play": play_ms, "k_mt_ahead": ahead_ms, "k_decode": dec_ms, "launches": n}
+
+
+DUMP_ARRAY_BYTES = 15_000_000  # per dumped array as float32; four arrays stay under 64 MB
+
+
+def dump_outputs(path, last):
+    """--dump-outputs: one launch's outputs ([10, B, ...] each, as rollout()
+    hands them to its caller) as path/<name>.npy in float32 (int8 / uint8 /
+    small int32 values: exact).  An array above DUMP_ARRAY_BYTES keeps a
+    sorted sample of its games, drawn without replacement from
+    numpy.random.default_rng(0): the same games in every run."""
+    os.makedirs(path, exist_ok=True)
+    for name, t in last.items():
+        B = t.shape[1]
+        per_game = t.numel() // B * 4
+        if per_game * B > DUMP_ARRAY_BYTES:
+            keep = np.sort(np.random.default_rng(0).choice(B, size=max(1, DUMP_ARRAY_BYTES // per_game), replace=False))
+            t = t[:, torch.as_tensor(keep, device=t.device)]
+        np.save(os.path.join(path, name + ".npy"), t.cpu().numpy().astype(np.float32))
 
 
 def make_out(env, games, with_obs, launches=1):
@@ -856,11 +897,13 @@ def pmc_traffic(rng, games):
 
 def main():
     args = parse()
+    legs = set(x for x in args.only.split(",") if x)
+    if legs - {"headline"} and not args.full:
+        raise SystemExit("bench: --only names legs beside the headline; they run under --full")
     n, spawn = resolve_world(args)
     if spawn:
         sys.exit(launch_ranks(n))
     world, rank, local = dist_setup(args)
-    legs = set(x for x in args.only.split(",") if x)
 
     def want(leg):
         return not legs or leg in legs
@@ -891,7 +934,9 @@ def main():
                        twist_every=args.twist_every, pipe_dec=args.pipe_dec)
     env.reset()
     out = make_out(env, B, not args.no_obs, args.launches_per_call)
-    wall, kern_ms, kt = time_rollouts(env, out, args.steps, args.warmup, world, args.launches_per_call)
+    dump = (lambda last: dump_outputs(args.dump_outputs, last)) if args.dump_outputs and rank == 0 else None
+    wall, kern_ms, kt = time_rollouts(env, out, args.steps, args.warmup, world, args.launches_per_call,
+                                      kernel_pass=args.full, after_timed=dump)
 
     # pipelined draws must never have run past the twisted words (checked
     # after the timed region; a nonzero count would void the parity claim)
@@ -904,32 +949,18 @@ def main():
     if world > 1:
         from rl_6_nimmt.distributed import max_over_ranks, reduce_agent_stats
 
-        wall, kern_ms, kt["k_play"], ahead = max_over_ranks([wall, kern_ms, kt["k_play"], kt.get("k_mt_ahead", 0.0)],
-                                                           device=env.device)
-        if "k_mt_ahead" in kt:
-            kt["k_mt_ahead"] = ahead
+        if args.full:
+            wall, kern_ms, kt["k_play"], ahead = max_over_ranks([wall, kern_ms, kt["k_play"], kt.get("k_mt_ahead", 0.0)],
+                                                               device=env.device)
+            if "k_mt_ahead" in kt:
+                kt["k_mt_ahead"] = ahead
+        else:
+            wall, = max_over_ranks([wall], device=env.device)
         reduce_agent_stats(tot)
 
     total_steps = world * B * STEPS_PER_LAUNCH * args.steps
     value = total_steps / wall
     launch_steps = B * STEPS_PER_LAUNCH
-    # dominant kernel = k_play (the game loop); its algorithmic bytes are the
-    # SURVEY.md §8(d) 377 B per env-step x the 655 360 env-steps of a launch,
-    # its duration the live HIP-event mean on its own stream (numpy mode: the
-    # twist-ahead k_mt_ahead runs concurrently on a side stream and is
-    # reported beside it; the whole step is `step_ms`)
-    play_ms = kt["k_play"]
-    twist_k = args.twist_every or LIB_TWIST_EVERY
-    play_mode = ("RNG_PHILOX" if args.rng != "numpy" else
-                 "RNG_NUMPY_DEC" if (kt.get("k_decode") or 0.0) > 0.0 else "RNG_NUMPY_PIPE")
-    achieved = launch_steps * ALGO_BYTES_PER_STEP / (play_ms * 1e-3) / 1e9
-    dec = play_mode == "RNG_NUMPY_DEC"
-    per_kernel, traffic_src = (pmc_traffic(args.rng if dec or args.rng != "numpy" else "numpy_ring", B)
-                               if not args.no_obs else (None, None))
-    traffic = per_kernel.get("k_play<4") if per_kernel else None
-    # bytes the counters saw per launch / its duration: below `frac` when the
-    # game state stays in VGPRs within a launch (SURVEY §8(d) counts it twice)
-    real_frac = traffic / (play_ms * 1e-3) / 1e9 / HBM_PEAK_GBS if traffic else None
     result = {
         "metric": "env-steps/sec at 65536 concurrent 4-player games, 1/2/4/8 MI355X",
         "value": value,
@@ -956,6 +987,36 @@ def main():
             "parallelism": f"dp{world} (independent game shards, no data-path collective)",
             "launches_per_call": args.launches_per_call,
         },
+        "episodes_checksum": {"episodes": int(eps.sum().item()) * world, "mean_score_per_seat": (tot / (eps.sum().item() * world)).tolist()},
+    }
+    if args.dump_outputs:
+        result["dumped_outputs"] = args.dump_outputs
+    if not args.full:  # a plain run: the headline alone
+        if rank == 0:
+            print(json.dumps(result), flush=True)
+        if world > 1:
+            import torch.distributed as dist
+
+            dist.destroy_process_group()
+        return
+    # dominant kernel = k_play (the game loop); its algorithmic bytes are the
+    # SURVEY.md §8(d) 377 B per env-step x the 655 360 env-steps of a launch,
+    # its duration the live HIP-event mean on its own stream (numpy mode: the
+    # twist-ahead k_mt_ahead runs concurrently on a side stream and is
+    # reported beside it; the whole step is `step_ms`)
+    play_ms = kt["k_play"]
+    twist_k = args.twist_every or LIB_TWIST_EVERY
+    play_mode = ("RNG_PHILOX" if args.rng != "numpy" else
+                 "RNG_NUMPY_DEC" if (kt.get("k_decode") or 0.0) > 0.0 else "RNG_NUMPY_PIPE")
+    achieved = launch_steps * ALGO_BYTES_PER_STEP / (play_ms * 1e-3) / 1e9
+    dec = play_mode == "RNG_NUMPY_DEC"
+    per_kernel, traffic_src = (pmc_traffic(args.rng if dec or args.rng != "numpy" else "numpy_ring", B)
+                               if not args.no_obs else (None, None))
+    traffic = per_kernel.get("k_play<4") if per_kernel else None
+    # bytes the counters saw per launch / its duration: below `frac` when the
+    # game state stays in VGPRs within a launch (SURVEY §8(d) counts it twice)
+    real_frac = traffic / (play_ms * 1e-3) / 1e9 / HBM_PEAK_GBS if traffic else None
+    result.update({
         "roofline": {
             "bound": "hbm",
             "achieved": achieved,
@@ -995,8 +1056,7 @@ def main():
             "step_traffic": per_kernel.get("_step") if per_kernel else None,
             "twist_every": twist_k if args.rng == "numpy" else None,
         },
-        "episodes_checksum": {"episodes": int(eps.sum().item()) * world, "mean_score_per_seat": (tot / (eps.sum().item() * world)).tolist()},
-    }
+    })
     if rank == 0 and world == 1 and not args.no_cpu and want("cpu"):
         result["cpu_baseline"] = cpu_baseline(args.cpu_seconds, args.rng)
     if world == 1 and not args.no_mcs and want("mcs"):

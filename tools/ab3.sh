@@ -20,7 +20,7 @@ for rep in $(seq 1 $REPS); do
     unset SECHS_LIB
     [ $v = dev ] && export SECHS_LIB=$R/$DEV
     [ $v = old ] && export SECHS_LIB=$R/$OLD
-    timeout -k 10 200 python bench.py $B > $OUT/ab_$v.json 2> $OUT/ab_$v.err || { tail -3 $OUT/ab_$v.err; exit 1; }
+    timeout -k 10 200 python bench.py --full $B > $OUT/ab_$v.json 2> $OUT/ab_$v.err || { tail -3 $OUT/ab_$v.err; exit 1; }
     summ $OUT/ab_$v.json $v
   done
 done

@@ -14,7 +14,7 @@ rc=$?; tail -1 $OUT/smoke.log; [ $rc -ne 0 ] && exit $rc
 for rep in 1 2; do
   for v in prod var; do
     unset SECHS_LIB; [ $v = var ] && export SECHS_LIB=$R/$VAR
-    timeout -k 10 400 python bench.py --only puct,mixed > $OUT/ab_$v.json 2> $OUT/ab_$v.err || { tail -3 $OUT/ab_$v.err; exit 1; }
+    timeout -k 10 400 python bench.py --full --only puct,mixed > $OUT/ab_$v.json 2> $OUT/ab_$v.err || { tail -3 $OUT/ab_$v.err; exit 1; }
     python -c "import json,sys; r=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); print(sys.argv[2], 'puct', round(r['extra_config4_puct']['value']/1e6,1), 'M league s/round', round(r['extra_config5_run_py_league']['s_per_round'],3))" $OUT/ab_$v.json $v
   done
 done

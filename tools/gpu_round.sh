@@ -21,7 +21,7 @@ if [ "$K" != "none" ]; then
   fi
   rc=$?; tail -25 $OUT/gpu_tests.log; fatal $rc pytest
 fi
-timeout -k 10 300 python bench.py --no-cpu --no-mcs --no-puct --no-scalar --no-league --no-mixed-league --no-dropin > $OUT/bench_head.json 2> $OUT/bench_head.err
+timeout -k 10 300 python bench.py --full --no-cpu --no-mcs --no-puct --no-scalar --no-league --no-mixed-league --no-dropin > $OUT/bench_head.json 2> $OUT/bench_head.err
 rc=$?; tail -3 $OUT/bench_head.err; fatal $rc bench_head
 python - $OUT/bench_head.json <<'PY'
 import json, sys
@@ -31,7 +31,7 @@ print("HEAD", round(r["value"] / 1e9, 3), "G/s ms", round(r["ms_per_step"], 4), 
       round(r.get("extra_config2_philox", {}).get("value", 0) / 1e9, 3))
 PY
 if [ -n "$LEGS" ]; then
-  timeout -k 10 600 python bench.py --only $LEGS ${BENCH_ARGS:-} > $OUT/bench_legs.json 2> $OUT/bench_legs.err
+  timeout -k 10 600 python bench.py --full --only $LEGS ${BENCH_ARGS:-} > $OUT/bench_legs.json 2> $OUT/bench_legs.err
   rc=$?; tail -3 $OUT/bench_legs.err; cat $OUT/bench_legs.json | cut -c1-3000; fatal $rc bench_legs
 fi
 echo done

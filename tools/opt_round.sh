@@ -17,7 +17,7 @@ summ() { python -c "import json,sys; r=json.loads(open(sys.argv[1]).read().strip
 for rep in $(seq 1 $REPS); do
   for v in new old; do
     if [ $v = old ]; then export SECHS_LIB=$R/$OLD; else unset SECHS_LIB; fi
-    timeout -k 10 200 python bench.py $B > $OUT/ab_$v.json 2> $OUT/ab_$v.err || { tail -3 $OUT/ab_$v.err; exit 1; }
+    timeout -k 10 200 python bench.py --full $B > $OUT/ab_$v.json 2> $OUT/ab_$v.err || { tail -3 $OUT/ab_$v.err; exit 1; }
     summ $OUT/ab_$v.json $v
   done
 done

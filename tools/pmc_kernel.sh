@@ -7,7 +7,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 TAG=${1:-cur}; KRX=${2:-k_play}; MODE=${3:-numpy}
 OUT=$R/gpurun_out/pmc_$TAG
 mkdir -p $OUT
-B="python3 bench.py --steps 5 --warmup 1 --no-cpu --no-mcs --no-puct --rng $MODE"
+B="python3 bench.py --full --steps 5 --warmup 1 --no-cpu --no-mcs --no-puct --rng $MODE"
 timeout -k 10 120 rocprofv3 --pmc FETCH_SIZE --kernel-include-regex "$KRX" --output-format csv -d $OUT/fetch -o run -- $B > $OUT/fetch.log 2>&1 || { tail $OUT/fetch.log; exit 1; }
 timeout -k 10 120 rocprofv3 --pmc WRITE_SIZE --kernel-include-regex "$KRX" --output-format csv -d $OUT/write -o run -- $B > $OUT/write.log 2>&1 || { tail $OUT/write.log; exit 1; }
 timeout -k 10 120 rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_LDS --kernel-include-regex "$KRX" --output-format csv -d $OUT/sq -o run -- $B > $OUT/sq.log 2>&1 || { tail $OUT/sq.log; exit 1; }

@@ -14,7 +14,7 @@ for rep in $(seq 1 $REPS); do
     unset SECHS_LIB; X=""
     [ $v = noobs ] && X="--no-obs"
     [ $v = probe ] && export SECHS_LIB=$R/$PROBE
-    timeout -k 10 200 python bench.py $B $X > $OUT/ab_$v.json 2> $OUT/ab_$v.err || { tail -3 $OUT/ab_$v.err; exit 1; }
+    timeout -k 10 200 python bench.py --full $B $X > $OUT/ab_$v.json 2> $OUT/ab_$v.err || { tail -3 $OUT/ab_$v.err; exit 1; }
     summ $OUT/ab_$v.json $v
   done
 done

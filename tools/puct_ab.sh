@@ -14,7 +14,7 @@ for rep in $(seq 1 $REPS); do
   for v in new old; do
     unset SECHS_LIB
     [ $v = old ] && export SECHS_LIB=$R/$OLD
-    timeout -k 10 400 python bench.py --only $LEGS > $OUT/ab_$v.json 2> $OUT/ab_$v.err || { tail -3 $OUT/ab_$v.err; exit 1; }
+    timeout -k 10 400 python bench.py --full --only $LEGS > $OUT/ab_$v.json 2> $OUT/ab_$v.err || { tail -3 $OUT/ab_$v.err; exit 1; }
     python - $OUT/ab_$v.json $v <<'PY'
 import json, sys
 r = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
@@ -28,7 +28,7 @@ PY
   done
 done
 unset SECHS_LIB
-cd /tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o run -- python3 $R/bench.py --only puct > $OUT/prof_bench.json 2> $OUT/prof_bench.err
+cd /tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o run -- python3 $R/bench.py --full --only puct > $OUT/prof_bench.json 2> $OUT/prof_bench.err
 rc=$?; [ $rc -ne 0 ] && { echo "prof rc=$rc"; tail -3 $OUT/prof_bench.err; exit $rc; }
 head -12 $OUT/prof/run_kernel_stats.csv | cut -d, -f1-4 | cut -c1-120
 echo done

@@ -13,7 +13,7 @@ timeout -k 10 300 python tools/acer_profile.py > $OUT/prof.txt 2>&1
 rc=$?; fatal $rc acerprof
 grep "learn()" $OUT/prof.txt
 for k in 1 0; do
-  SECHS_ACER_SPLITK=$k timeout -k 10 400 python bench.py --only mixed > $OUT/mixed_$k.json 2> $OUT/mixed_$k.err
+  SECHS_ACER_SPLITK=$k timeout -k 10 400 python bench.py --full --only mixed > $OUT/mixed_$k.json 2> $OUT/mixed_$k.err
   rc=$?; fatal $rc mixed
   echo "splitk=$k"; python tools/ab_line.py mixed $OUT/mixed_$k.json | cut -c1-400
 done

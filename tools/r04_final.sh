@@ -12,7 +12,7 @@ rc=$?; tail -3 $OUT/pytest_gpu.log; fatal $rc pytest
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $OUT/smoke.log 2>&1
 rc=$?; tail -1 $OUT/smoke.log; fatal $rc smoke
 for rep in 1 2; do
-  timeout -k 10 400 python bench.py > $OUT/bench_$rep.json 2> $OUT/bench_$rep.err
+  timeout -k 10 400 python bench.py --full > $OUT/bench_$rep.json 2> $OUT/bench_$rep.err
   rc=$?; fatal $rc bench
   python tools/ab_line.py head $OUT/bench_$rep.json bench rep=$rep
   python - $OUT/bench_$rep.json <<'PY'

@@ -7,7 +7,7 @@ OUT=$R/gpurun_out/${1:-r04_prof2}
 mkdir -p $OUT
 fatal() { [ "$1" -ge 124 ] && { echo "fatal rc=$1 in $2"; exit $1; }; return 0; }
 shrink() { find $R/gpurun_out -name "*.db" -size +1M -delete; find $R/gpurun_out -name "*kernel_trace.csv" -size +1M -delete; }
-timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/kt_head -o run -- python3 bench.py --only headline --steps 20 > $OUT/kt_head.log 2>&1
+timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/kt_head -o run -- python3 bench.py --full --only headline --steps 20 > $OUT/kt_head.log 2>&1
 rc=$?; echo "kt_head rc=$rc"; fatal $rc kt_head
 [ $rc -ne 0 ] && { tail -5 $OUT/kt_head.log; exit 1; }
 python3 tools/db_kstats.py $OUT/kt_head $OUT/kt_head_kernel_stats.csv && python3 tools/trace_gaps.py $OUT/kt_head > $OUT/kt_head_gaps.txt 2>&1; shrink

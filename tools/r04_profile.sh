@@ -8,7 +8,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 TAG=${1:-r04}
 OUT=$R/gpurun_out/prof_$TAG
 mkdir -p $OUT
-B="python3 $R/bench.py --steps 100 --warmup 3 --no-cpu --no-mcs --no-puct --no-scalar --no-league --no-mixed-league --no-dropin --no-philox"
+B="python3 $R/bench.py --full --steps 100 --warmup 3 --no-cpu --no-mcs --no-puct --no-scalar --no-league --no-mixed-league --no-dropin --no-philox"
 cd /tmp
 timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt -o run -- $B > $OUT/kt.log 2>&1 || { tail $OUT/kt.log; exit 1; }
 python3 $R/tools/trace_gaps.py $OUT/kt/run_kernel_trace.csv > $OUT/gaps.txt 2>&1; cat $OUT/gaps.txt

@@ -16,11 +16,11 @@ rc=$?; tail -2 $OUT/tests_league.log; fatal $rc pytest_league
 [ $rc -ne 0 ] && exit 1
 for rep in 1 2 3; do
   for f in 0 3; do
-    SECHS_PIPE_FLAGS=$f timeout -k 10 200 python bench.py --only headline > $OUT/head_f${f}_$rep.json 2> $OUT/head_f${f}_$rep.err
+    SECHS_PIPE_FLAGS=$f timeout -k 10 200 python bench.py --full --only headline > $OUT/head_f${f}_$rep.json 2> $OUT/head_f${f}_$rep.err
     rc=$?; fatal $rc head
     python tools/ab_line.py head $OUT/head_f${f}_$rep.json flags=$f rep=$rep
   done
 done
-(cd /tmp && SECHS_PIPE_FLAGS=3 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/prof_head3 -o run -- python3 $R/bench.py --only headline --steps 20 > $OUT/prof_head3.log 2>&1)
+(cd /tmp && SECHS_PIPE_FLAGS=3 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/prof_head3 -o run -- python3 $R/bench.py --full --only headline --steps 20 > $OUT/prof_head3.log 2>&1)
 rc=$?; echo "rocprof head3 rc=$rc"; fatal $rc rocprof_head3
 echo done

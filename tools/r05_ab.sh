@@ -14,7 +14,7 @@ for rep in 1 2; do
     for cfg in "${CFGS[@]}"; do
       set -- $cfg
       nm=b_r$1_k$2_q$3_s${ser}_$rep
-      SECHS_PIPE_SERIAL=$ser timeout -k 10 200 python bench.py --only headline --steps 200 --warmup 10 --twist-round $1 --twist-every $2 --play-quad $3 > $OUT/$nm.json 2> $OUT/$nm.err || { tail $OUT/$nm.err; exit 1; }
+      SECHS_PIPE_SERIAL=$ser timeout -k 10 200 python bench.py --full --only headline --steps 200 --warmup 10 --twist-round $1 --twist-every $2 --play-quad $3 > $OUT/$nm.json 2> $OUT/$nm.err || { tail $OUT/$nm.err; exit 1; }
       python -c "import json;d=json.load(open('$OUT/$nm.json'));r=d['roofline'];print('serial $ser round $1 every $2 quad $3: %.3e env-steps/s, ms/step %.4f, play %.4f, ahead %.4f'%(d['value'],d['ms_per_step'],r['kernel_ms'],r['concurrent']['kernel_ms']))"
     done
   done

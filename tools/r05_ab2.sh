@@ -13,7 +13,7 @@ for rep in 1 2 3; do
   for cfg in "2 1" "1 0" "3 1"; do
     set -- $cfg
     nm=h_k$1_r$2_$rep
-    timeout -k 10 200 python bench.py --only headline --steps 200 --warmup 10 --twist-every $1 --twist-round $2 > $OUT/$nm.json 2> $OUT/$nm.err || { tail $OUT/$nm.err; exit 1; }
+    timeout -k 10 200 python bench.py --full --only headline --steps 200 --warmup 10 --twist-every $1 --twist-round $2 > $OUT/$nm.json 2> $OUT/$nm.err || { tail $OUT/$nm.err; exit 1; }
     python -c "import json;d=json.load(open('$OUT/$nm.json'));r=d['roofline'];print('every $1 round $2: %.3e env-steps/s, ms/step %.4f, play %.4f, ahead %s'%(d['value'],d['ms_per_step'],r['kernel_ms'],r['concurrent']['kernel_ms']))"
   done
 done

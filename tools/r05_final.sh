@@ -14,11 +14,11 @@ rc=$?; tail -3 $OUT/pytest_gpu.log; fatal $rc pytest
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $OUT/smoke.log 2>&1
 rc=$?; tail -1 $OUT/smoke.log; fatal $rc smoke
 fi
-timeout -k 10 400 python bench.py > $OUT/bench_1.json 2> $OUT/bench_1.err
+timeout -k 10 400 python bench.py --full > $OUT/bench_1.json 2> $OUT/bench_1.err
 rc=$?; fatal $rc bench; [ $rc -ne 0 ] && { tail $OUT/bench_1.err; exit 1; }
 python tools/ab_line.py head $OUT/bench_1.json bench rep=1
 cd /tmp
-B="python3 $R/bench.py --only headline --steps 20 --warmup 5"
+B="python3 $R/bench.py --full --only headline --steps 20 --warmup 5"
 timeout -k 10 180 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kstats -o run -- $B > $OUT/kstats.log 2>&1 || { tail $OUT/kstats.log; exit 1; }
 timeout -k 10 120 rocprofv3 --pmc FETCH_SIZE --kernel-include-regex "k_play|k_mt_ahead" --output-format csv -d $OUT/fetch -o run -- $B > $OUT/fetch.log 2>&1 || { tail $OUT/fetch.log; exit 1; }
 timeout -k 10 120 rocprofv3 --pmc WRITE_SIZE --kernel-include-regex "k_play|k_mt_ahead" --output-format csv -d $OUT/write -o run -- $B > $OUT/write.log 2>&1 || { tail $OUT/write.log; exit 1; }

@@ -9,7 +9,7 @@ SECHS_TEST_TWIST_EVERY=5 timeout -k 10 600 python -u -m pytest tests/test_gpu_en
 for rep in 1 2; do
   for k in 4 5; do
     nm=k${k}_$rep
-    timeout -k 10 200 python bench.py --only headline --steps 200 --warmup 10 --twist-every $k > $OUT/$nm.json 2> $OUT/$nm.err || { tail $OUT/$nm.err; exit 1; }
+    timeout -k 10 200 python bench.py --full --only headline --steps 200 --warmup 10 --twist-every $k > $OUT/$nm.json 2> $OUT/$nm.err || { tail $OUT/$nm.err; exit 1; }
     python -c "import json;d=json.load(open('$OUT/$nm.json'));r=d['roofline'];print('K $k: %.3e env-steps/s, ms/step %.4f, play %.4f'%(d['value'],d['ms_per_step'],r['kernel_ms']))"
   done
 done

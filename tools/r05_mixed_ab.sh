@@ -8,7 +8,7 @@ mkdir -p $OUT
 for rep in 1 2; do
   for ro in 1 0; do
     nm=mixed_ro${ro}_$rep
-    SECHS_PUCT_ROLLOUTS=$ro timeout -k 10 400 python bench.py --only mixed > $OUT/$nm.json 2> $OUT/$nm.err || { tail $OUT/$nm.err; exit 1; }
+    SECHS_PUCT_ROLLOUTS=$ro timeout -k 10 400 python bench.py --full --only mixed > $OUT/$nm.json 2> $OUT/$nm.err || { tail $OUT/$nm.err; exit 1; }
     python - $OUT/$nm.json $ro <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1]))["extra_config5_run_py_league"]

@@ -20,7 +20,7 @@ for rep in 1 2; do
   run FD_QUAD=1 FD_EVERY=2 FD_ROUND=1
 done
 for rb in 16 0; do
-  SECHS_PUCT_DEAL_BATCH=$rb timeout -k 10 300 python bench.py --only puct > $OUT/puct_rb$rb.json 2> $OUT/puct_rb$rb.err || { tail $OUT/puct_rb$rb.err; exit 1; }
+  SECHS_PUCT_DEAL_BATCH=$rb timeout -k 10 300 python bench.py --full --only puct > $OUT/puct_rb$rb.json 2> $OUT/puct_rb$rb.err || { tail $OUT/puct_rb$rb.err; exit 1; }
   python -c "import json;d=json.load(open('$OUT/puct_rb$rb.json'))['extra_config4_puct'];print('config4 deal batch $rb: %.3e playout env-steps/s, %.1f TFLOP/s'%(d['value'],d['policy_tflops']))"
 done
 echo done

@@ -10,9 +10,9 @@ mkdir -p $OUT
 cd $R
 SECHS_LIB=$R/rl-6-nimmt_amd/libsechs_devprof.so timeout -k 10 180 python tools/phase_prof.py 65536 40 numpy > $OUT/phase.json 2> $OUT/phase.err || { tail $OUT/phase.err; exit 1; }
 cat $OUT/phase.json
-timeout -k 10 200 python bench.py --only headline --steps 200 --warmup 20 > $OUT/bench_head.json 2> $OUT/bench_head.err && python tools/ab_line.py head $OUT/bench_head.json base
+timeout -k 10 200 python bench.py --full --only headline --steps 200 --warmup 20 > $OUT/bench_head.json 2> $OUT/bench_head.err && python tools/ab_line.py head $OUT/bench_head.json base
 cd /tmp
-B="python3 $R/bench.py --only headline --steps 40 --warmup 8"
+B="python3 $R/bench.py --full --only headline --steps 40 --warmup 8"
 timeout -k 10 180 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kstats -o run -- $B > $OUT/kstats.log 2>&1 || { tail $OUT/kstats.log; exit 1; }
 timeout -k 10 120 rocprofv3 --pmc FETCH_SIZE --kernel-include-regex "k_play|k_mt_ahead" --output-format csv -d $OUT/fetch -o run -- $B > $OUT/fetch.log 2>&1 || { tail $OUT/fetch.log; exit 1; }
 timeout -k 10 120 rocprofv3 --pmc WRITE_SIZE --kernel-include-regex "k_play|k_mt_ahead" --output-format csv -d $OUT/write -o run -- $B > $OUT/write.log 2>&1 || { tail $OUT/write.log; exit 1; }

@@ -12,12 +12,12 @@ timeout -k 10 600 python -u -m pytest tests/test_gpu_env.py -x -v --timeout 240 
 rc=$?; tail -4 $OUT/pytest_env.log; [ $rc -ne 0 ] && exit $rc
 for rep in 1 2; do
   for d in 1 0; do
-    timeout -k 10 200 python bench.py --only headline --steps 200 --warmup 20 --pipe-dec $d > $OUT/head_d${d}_$rep.json 2> $OUT/head_d${d}_$rep.err || { tail $OUT/head_d${d}_$rep.err; exit 1; }
+    timeout -k 10 200 python bench.py --full --only headline --steps 200 --warmup 20 --pipe-dec $d > $OUT/head_d${d}_$rep.json 2> $OUT/head_d${d}_$rep.err || { tail $OUT/head_d${d}_$rep.err; exit 1; }
     python tools/ab_line.py head $OUT/head_d${d}_$rep.json dec=$d rep=$rep
   done
 done
 cd /tmp
-timeout -k 10 180 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kstats -o run -- python3 $R/bench.py --only headline --steps 40 --warmup 8 > $OUT/kstats.log 2>&1 || { tail $OUT/kstats.log; exit 1; }
+timeout -k 10 180 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kstats -o run -- python3 $R/bench.py --full --only headline --steps 40 --warmup 8 > $OUT/kstats.log 2>&1 || { tail $OUT/kstats.log; exit 1; }
 cd $R
 head -6 $OUT/kstats/run_kernel_stats.csv
 python3 tools/group_trace.py $OUT/kstats/run_kernel_trace.csv 4 > $OUT/groups.json && cat $OUT/groups.json

@@ -8,13 +8,13 @@ OUT=$R/gpurun_out/${1:-r06_final}
 mkdir -p $OUT
 cd $R
 fatal() { [ "$1" -ge 124 ] && { echo "fatal rc=$1 in $2"; exit $1; }; return 0; }
-timeout -k 10 500 python bench.py > $OUT/bench_1.json 2> $OUT/bench_1.err
+timeout -k 10 500 python bench.py --full > $OUT/bench_1.json 2> $OUT/bench_1.err
 rc=$?; fatal $rc bench; [ $rc -ne 0 ] && { tail $OUT/bench_1.err; exit 1; }
 python tools/ab_line.py head $OUT/bench_1.json bench rep=1
 python tools/ab_line.py puct $OUT/bench_1.json bench
 python tools/ab_line.py mixed $OUT/bench_1.json bench
 cd /tmp
-B="python3 $R/bench.py --only headline --steps 40 --warmup 8"
+B="python3 $R/bench.py --full --only headline --steps 40 --warmup 8"
 timeout -k 10 180 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kstats -o run -- $B > $OUT/kstats.log 2>&1 || { tail $OUT/kstats.log; exit 1; }
 timeout -k 10 120 rocprofv3 --pmc FETCH_SIZE --kernel-include-regex "k_play|k_mt_ahead|k_decode" --output-format csv -d $OUT/fetch -o run -- $B > $OUT/fetch.log 2>&1 || { tail $OUT/fetch.log; exit 1; }
 timeout -k 10 120 rocprofv3 --pmc WRITE_SIZE --kernel-include-regex "k_play|k_mt_ahead|k_decode" --output-format csv -d $OUT/write -o run -- $B > $OUT/write.log 2>&1 || { tail $OUT/write.log; exit 1; }

@@ -10,6 +10,6 @@ rc=$?; tail -2 $OUT/pytest_puct.log; [ $rc -ne 0 ] && exit $rc
 SECHS_LIB=$R/rl-6-nimmt_amd/libsechs_prof.so timeout -k 10 300 python tools/puct_phase_prof.py 8192 > $OUT/phase_puct.json || exit 1
 cat $OUT/phase_puct.json
 for rep in 1 2; do
-  timeout -k 10 200 python bench.py --only puct > $OUT/puct_$rep.json 2> $OUT/puct_$rep.err || { tail $OUT/puct_$rep.err; exit 1; }
+  timeout -k 10 200 python bench.py --full --only puct > $OUT/puct_$rep.json 2> $OUT/puct_$rep.err || { tail $OUT/puct_$rep.err; exit 1; }
   python tools/ab_line.py puct $OUT/puct_$rep.json rep=$rep
 done

@@ -21,12 +21,12 @@ for rep in 1 2; do
   for cfg in "1 1 0" "1 2 0" "0 1 0" "1 2 1" "1 1 1"; do
     set -- $cfg
     nm=b_r$1_k$2_q$3_$rep
-    timeout -k 10 200 python bench.py --only headline --steps 200 --warmup 10 --twist-round $1 --twist-every $2 --play-quad $3 > $OUT/$nm.json 2> $OUT/$nm.err || { tail $OUT/$nm.err; exit 1; }
+    timeout -k 10 200 python bench.py --full --only headline --steps 200 --warmup 10 --twist-round $1 --twist-every $2 --play-quad $3 > $OUT/$nm.json 2> $OUT/$nm.err || { tail $OUT/$nm.err; exit 1; }
     python -c "import json;d=json.load(open('$OUT/$nm.json'));r=d['roofline'];print('round $1 every $2 quad $3: %.3e env-steps/s, ms/step %.4f, play %.4f, ahead %.4f'%(d['value'],d['ms_per_step'],r['kernel_ms'],r['concurrent']['kernel_ms']))"
   done
 done
 for l1 in mfma seats; do
-  SECHS_MLP_LAYER1=$l1 timeout -k 10 300 python bench.py --only puct > $OUT/puct_$l1.json 2> $OUT/puct_$l1.err || { tail $OUT/puct_$l1.err; exit 1; }
+  SECHS_MLP_LAYER1=$l1 timeout -k 10 300 python bench.py --full --only puct > $OUT/puct_$l1.json 2> $OUT/puct_$l1.err || { tail $OUT/puct_$l1.err; exit 1; }
   python -c "import json;d=json.load(open('$OUT/puct_$l1.json'))['extra_config4_puct'];print('config4 $l1: %.3e playout env-steps/s, %.1f TFLOP/s'%(d['value'],d['policy_tflops']))"
 done
 echo done
