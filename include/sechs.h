@@ -479,6 +479,59 @@ sn_status sn_policy_sample(sn_env* env, const sn_puct* q, const float* logits, i
 sn_status sn_puct_score(int64_t num, const int32_t* n, const int32_t* stats, const int32_t* hist, const float* probs,
                         double c_puct, double* pucts, int32_t* choice, void* stream);
 
+/* ---- Prioritised experience replay (utils/replay_buffer.py:15-203) ------
+   The SumTree + PriorityReplayBuffer of the DQN family on the device.  An
+   sn_per handle owns a sum tree of 2*capacity-1 f64 nodes in the reference's
+   implicit-heap layout for every capacity (root 0, children of i at 2i+1 and
+   2i+2, leaves at capacity-1 .. 2*capacity-2, data slot = leaf - capacity + 1:
+   the tree indices sample returns go back into update, so the layout is part
+   of the interface) and an optional payload ring [capacity][row_bytes].
+   After store and update every internal node is left + right, recomputed
+   pairwise from the leaves (the reference adds `change` along one path,
+   replay_buffer.py:16-27: equal up to its rounding drift).  The pointer and
+   the item counter live on the host and move when a call is enqueued, so no
+   call synchronises; calls of one handle belong on one stream.
+   Two reference quirks are kept (replay_buffer.py:81-104,160-166):
+     - num_items grows on every store that does not wrap the pointer, also
+       after the buffer is full: len = stores - wraps, past the capacity
+       (capacity 5: 35 after 43 stores);
+     - min_leaf, the normaliser of the importance weights, is the minimum
+       over leaves [0, min(num_items, capacity)): right after the first wrap
+       the last leaf is left out. */
+typedef struct sn_per sn_per; /* opaque */
+/* capacity >= 2 (the reference cannot sample from a one-slot buffer);
+   row_bytes 0 (no payload) or a multiple of 16 */
+sn_status sn_per_create(sn_per** out, int64_t capacity, int64_t row_bytes, int device);
+sn_status sn_per_destroy(sn_per* per);
+/* the host counters: SumTree.capacity, .data_pointer, .num_items (each may be NULL) */
+sn_status sn_per_info(const sn_per* per, int64_t* capacity, int64_t* pointer, int64_t* num_items);
+/* m sequential PriorityReplayBuffer.store calls (replay_buffer.py:150-158),
+   1 <= m <= capacity: slots pointer .. pointer+m-1 modulo capacity get the
+   priority M = the maximum over all leaves before the call, or 1.0 if that
+   is 0 (writing M never changes the maximum, so M is the same for the whole
+   batch, as in the reference's loop).  rows: [m][row_bytes] payload copied
+   into the same slots (16-byte aligned), or NULL. */
+sn_status sn_per_store(sn_per* per, int64_t m, const void* rows, void* stream);
+/* PriorityReplayBuffer.sample(n) (replay_buffer.py:160-186) with the caller's
+   uniforms u [n] f64 in [0,1): sample i descends with v = seg*i + u[i]*seg,
+   seg = total/n (`v <= left` goes left, else subtract and go right,
+   :43-60), in the reference's operation order without FP contraction.
+   tree_idx [n] uint32; priority [n] f64 = the leaf; is_weight [n] f64 =
+   ((p/total)/min_prob)^-beta, min_prob = min_leaf/total; rows_out
+   [n][row_bytes] = the payload rows of the sampled slots.  priority,
+   is_weight and rows_out may be NULL.  An empty replay is SN_EINVAL (the
+   reference's np.min raises). */
+sn_status sn_per_sample(sn_per* per, int64_t n, const double* u, double beta, uint32_t* tree_idx, double* priority,
+                        double* is_weight, void* rows_out, void* stream);
+/* PriorityReplayBuffer.batch_update (replay_buffer.py:188-200): leaf
+   tree_idx[i] = min(abs_err[i] + eps, upper)^alpha.  Where an index repeats
+   the highest position wins (the reference's sequential loop); indices
+   outside the leaf range are skipped, not written. */
+sn_status sn_per_update(sn_per* per, int64_t n, const uint32_t* tree_idx, const double* abs_err, double eps,
+                        double upper, double alpha, void* stream);
+/* the 2*capacity-1 nodes (tests, cloning) */
+sn_status sn_per_tree(sn_per* per, double* tree_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

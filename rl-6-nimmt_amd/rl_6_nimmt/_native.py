@@ -110,6 +110,13 @@ SIGNATURES = {
     "sn_pcv_choose": ([_P, _P, _P, _P, _P, _P, _P, _P], _I),
     "sn_policy_sample": ([_P, _P, _P, _P, _P, _P, _P, _P], _I),
     "sn_puct_score": ([_I64, _P, _P, _P, _P, ctypes.c_double, _P, _P, _P], _I),
+    "sn_per_create": ([ctypes.POINTER(_P), _I64, _I64, _I], _I),
+    "sn_per_destroy": ([_P], _I),
+    "sn_per_info": ([_P, _P, _P, _P], _I),
+    "sn_per_store": ([_P, _I64, _P, _P], _I),
+    "sn_per_sample": ([_P, _I64, _P, ctypes.c_double, _P, _P, _P, _P, _P], _I),
+    "sn_per_update": ([_P, _I64, _P, _P, ctypes.c_double, ctypes.c_double, ctypes.c_double, _P], _I),
+    "sn_per_tree": ([_P, _P, _P], _I),
 }
 
 

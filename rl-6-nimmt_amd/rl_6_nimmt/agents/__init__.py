@@ -3,20 +3,31 @@
 Kept: Agent, DrunkHamster ("random"), MCSAgent ("mcts"), PolicyMCSAgent
 ("pmcs"), PUCTAgent ("puct"), BatchedReinforceAgent ("reinforce"),
 BatchedACERAgent ("acer") and PUCTCustomedAgent (exported, not in the
-registry -- as in the reference).  The DQN family (replay/PER buffers) and
-the human UI are outside this build's scope and absent from
-AGENTS.
+registry -- as in the reference).
+
+The DQN family's four base agents -- DQNVanilla ("dqn"), DDQNAgent ("ddqn"),
+DQN_PRBAgent ("dqn_prb"), DDQN_PRBAgent ("ddqn_prb") -- are drop-ins on the
+device prioritised replay (rl_6_nimmt/replay.py) and registered in
+DQN_AGENTS, not in AGENTS: every AGENTS entry has a batched-league engine,
+and the batched league DQN learner is not built yet (league.agent_kind raises
+NotImplementedError for them).  Not built: the duelling, noisy and n-step DQN
+variants and the human UI.
 """
 from .base import Agent
 from .random import DrunkHamster
 from .mcts import BaseMCAgent, MCSAgent, PolicyMCSAgent, PUCTAgent, PUCTCustomedAgent
 from .policy import BatchedReinforceAgent
 from .actor_critic import BatchedACERAgent
+from .dqn import DQNVanilla, DDQNAgent, DQN_PRBAgent, DDQN_PRBAgent
 
 HUMAN = "human"
 RANDOM_AGENT = "random"
 REINFORCE = "reinforce"
 ACER = "acer"
+DQN = "dqn"
+DDQN = "ddqn"
+DQN_PRB = "dqn_prb"
+DDQN_PRB = "ddqn_prb"
 MCS = "mcts"
 PMCS = "pmcs"
 PUCT = "puct"
@@ -28,4 +39,11 @@ AGENTS = {
     MCS: MCSAgent,
     PMCS: PolicyMCSAgent,
     PUCT: PUCTAgent,
+}
+
+DQN_AGENTS = {
+    DQN: DQNVanilla,
+    DDQN: DDQNAgent,
+    DQN_PRB: DQN_PRBAgent,
+    DDQN_PRB: DDQN_PRBAgent,
 }

@@ -9,7 +9,7 @@ data (inputs + expected outputs); no reference source is copied.
 The reference imports three third-party modules that are absent from this
 image (gym, numba, multi_elo).  None of them takes part in the arithmetic
 being pinned (env.py only subclasses gym.Env and builds Discrete/Box space
-descriptors, numba only decorates the out-of-scope PER buffer, multi_elo is
+descriptors, numba only decorates the PER buffer's helpers (F15 / F16 below), multi_elo is
 only called by Tournament._compute_elos, which is not exercised here), so the
 generator puts attribute-holder stand-ins for them on sys.path in a
 temporary directory before importing the reference.
@@ -51,6 +51,24 @@ Fixture families (SURVEY.md §4 "What the build must add"):
                            (every metric, copies / max_players /
                            max_per_descendant combinations, two or three
                            evolves): games and the roster after each evolve
+  F15 per_traces.json    seeded PriorityReplayBuffer traces (store / sample /
+                           batch_update rounds): per round the uniforms, the
+                           errors, the sampled tree indices, priorities and
+                           weights, beta and len; tree snapshots (the float
+      per_traces.npz       arrays in the .npz)
+  F16 dqn_games.json     seeded GameSession(<DQN agent>, DrunkHamster x 3)
+      dqn_weights.npz      training sessions of DQNVanilla, DDQNAgent,
+                           DQN_PRBAgent and DDQN_PRBAgent (default epsilon
+                           schedule, and a constant epsilon of 0.3): per step
+                           the move, info["value"] and epsilon; the loss of
+                           every learn(); the PER tree indices sampled;
+                           initial and final weights
+
+F15 / F16 pin the reference's *Python* semantics of the prioritised replay:
+with the stand-in numba.jit the sampler `_get_leaf_ids` runs as plain Python
+and draws from Python's global `random`.  Under real numba the jitted sampler
+draws from numba's own generator, which `random.seed` does not reach, so the
+reference is not reproducible there at all.
 """
 import argparse
 import json
@@ -944,6 +962,211 @@ def gen_evolve(ref, out):
                                "rosters in the reference's dict order", "cases": cases}, f)
 
 
+# ----------------------------------------------------------------------------
+# F15: PriorityReplayBuffer traces
+# ----------------------------------------------------------------------------
+PER_SHAPES = [(5, 3, 4, 40), (8, 8, 8, 40), (100, 60, 10, 120), (100, 250, 16, 120)]  # (cap, nstore, n, rounds)
+PER_MARGIN = 1e-10  # of the total priority
+
+
+def _per_margin(tree, n, us):
+    """smallest |v - threshold| / total over the descents of sample(n) with uniforms us"""
+    total = tree[0]
+    seg = total / n
+    worst = float("inf")
+    for i, u in enumerate(us):
+        v = seg * i + u * seg
+        node = 0
+        while 2 * node + 1 < len(tree):
+            left = tree[2 * node + 1]
+            worst = min(worst, abs(v - left) / total)
+            if v <= left:
+                node = 2 * node + 1
+            else:
+                v -= left
+                node = 2 * node + 2
+    return worst
+
+
+def _recorded_sample(buf, n, sample=None):
+    """buf.sample(n) and the uniforms it drew from Python's `random`, and the descents' margin"""
+    import random
+
+    tree = buf.tree.tree.copy()
+    before = random.getstate()
+    out = (sample or buf.sample)(n)
+    after = random.getstate()
+    random.setstate(before)
+    us = [random.random() for _ in range(n)]
+    assert random.getstate() == after, "sample(n) drew something other than n uniforms"
+    return out, us, _per_margin(tree, n, us), tree
+
+
+def gen_per(ref, out):
+    import random
+
+    from rl_6_nimmt.utils.replay_buffer import PriorityReplayBuffer
+
+    traces, arrays = [], {}
+    for cap, nstore, n, rounds in PER_SHAPES:
+        random.seed(cap)
+        np.random.seed(cap)
+        buf = PriorityReplayBuffer(max_length=cap)
+        stores = 0
+        for _ in range(nstore):
+            buf.store(k=stores)
+            stores += 1
+        rec, snaps, repeats, worst = [], {}, 0, float("inf")
+        for r in range(rounds):
+            buf.store(k=stores)
+            stores += 1
+            (idx, weights, batch), us, margin, tree = _recorded_sample(buf, n)
+            worst = min(worst, margin)
+            repeats += len(set(idx.tolist())) < n
+            errors = np.random.random_sample(n) * 1.5
+            sent = errors.copy()  # batch_update adds epsilon in place
+            buf.batch_update(idx, sent)
+            rec.append({"u": us, "errors": errors, "idx": [int(x) for x in idx], "weights": weights,
+                        "priorities": tree[idx], "beta": float(buf.beta), "len": len(buf)})
+            if (r + 1) % 20 == 0 or r == rounds - 1:
+                snaps[r] = buf.tree.tree.copy()
+        assert worst >= PER_MARGIN, f"capacity {cap}: a descent within {worst} of a threshold"
+        assert repeats >= 1, f"capacity {cap}: no round sampled an index twice"
+        ti = len(traces)
+        for key in ("u", "errors", "weights", "priorities", "beta"):
+            arrays[f"t{ti}_{key}"] = np.array([rd[key] for rd in rec], dtype=np.float64)
+        arrays[f"t{ti}_tree"] = np.stack([snaps[r] for r in sorted(snaps)])
+        arrays[f"t{ti}_idx"] = np.array([rd["idx"] for rd in rec], dtype=np.int64)
+        arrays[f"t{ti}_len"] = np.array([rd["len"] for rd in rec], dtype=np.int64)
+        traces.append({"capacity": cap, "nstore": nstore, "n": n, "rounds": rounds,
+                       "snapshots": sorted(snaps), "min_margin": worst, "rounds_with_repeats": int(repeats)})
+    np.savez_compressed(os.path.join(out, "per_traces.npz"), **arrays)
+    with open(os.path.join(out, "per_traces.json"), "w") as f:
+        json.dump({"protocol": "random.seed(cap); np.random.seed(cap); buf = PriorityReplayBuffer(cap); nstore x "
+                               "store(k=<store count>); per round: store, sample(n), batch_update(idx, errors) with "
+                               "errors = np.random.random_sample(n) * 1.5.  per_traces.npz, t<i>_*, [round][...]: idx = "
+                               "the tree indices sampled, len = len(buf) (int64); f64: u = the uniforms sample drew from random.random(), errors "
+                               "(before epsilon is added), weights, priorities = the leaves sampled, beta; tree = all "
+                               "nodes after each round of `snapshots`.  min_margin = smallest |v - threshold| / total "
+                               "over all descents (asserted >= 1e-10).  Python semantics of the sampler (numba.jit is "
+                               "a no-op here)",
+                   "traces": traces}, f)
+
+
+# ----------------------------------------------------------------------------
+# F16: the DQN agents in training sessions
+# ----------------------------------------------------------------------------
+DQN_CLASSES = ["DQNVanilla", "DDQNAgent", "DQN_PRBAgent", "DDQN_PRBAgent"]
+DQN_KW = {"history_length": 256, "minibatch": 16}
+DQN_GAMES = 6
+DQN_GAP = 1e-3
+# the agents' priorities are float32 (numpy keeps the tensor's dtype through the power): two libm's powf may
+# differ by an ulp, 6e-8 of a leaf, so the sessions keep well clear of that, not just of PER_MARGIN
+DQN_MARGIN = 1e-6
+
+
+def _dqn_session(cls_name, seed, eps_const):
+    """one seeded session, or None if the seed is too close to a tie"""
+    import random
+
+    import torch
+    from rl_6_nimmt import agents as A
+    from rl_6_nimmt.play import GameSession
+
+    torch.manual_seed(seed)
+    kw = dict(DQN_KW)
+    if eps_const is not None:
+        kw["eps_func"] = lambda episode, _c=eps_const: _c
+    ag = getattr(A, cls_name)(**kw)
+    agents = [ag] + [A.DrunkHamster() for _ in range(3)]
+    ag.train()
+    init = {k: v.detach().numpy().astype(np.float32).copy() for k, v in ag.state_dict().items()}
+    tr = {"steps": [], "losses": [], "per_idx": []}
+    worst = {"gap": float("inf"), "margin": float("inf")}
+    sel, lrn = ag._action_selection, ag.learn
+
+    def sel_rec(scores, **k):
+        act, info = sel(scores, **k)
+        if info["value"] != -1:  # greedy: `scores` is masked in place by now
+            top = np.sort(scores.numpy()[list(k["legal_actions"])])[::-1]
+            if len(top) > 1:
+                worst["gap"] = min(worst["gap"], float(top[0] - top[1]))
+        tr["steps"].append([int(act), float(info["value"]), float(info["eps"])])
+        return act, info
+
+    def lrn_rec(*a, **k):
+        loss = lrn(*a, **k)
+        tr["losses"].append(float(loss[0]))
+        return loss
+
+    ag._action_selection, ag.learn = sel_rec, lrn_rec
+    prb = "PRB" in cls_name
+    if prb:
+        buf = ag.history
+        smp = buf.sample
+
+        def smp_rec(n):
+            res, us, margin, _ = _recorded_sample(buf, n, smp)
+            worst["margin"] = min(worst["margin"], margin)
+            tr["per_idx"].append([int(x) for x in res[0]])
+            return res
+
+        buf.sample = smp_rec
+    np.random.seed(seed)
+    random.seed(seed)
+    sess = GameSession(*agents)
+    for _ in range(DQN_GAMES):
+        sess.play_game()
+    if worst["gap"] < DQN_GAP or worst["margin"] < DQN_MARGIN:
+        return None
+    final = {k: v.detach().numpy().astype(np.float32).copy() for k, v in ag.state_dict().items()}
+    rec = {"agent": cls_name, "seed": seed, "games": DQN_GAMES, "kwargs": DQN_KW, "eps_const": eps_const,
+           "results": [[int(x) for x in r] for r in sess.results],            "greedy_steps": int(sum(1 for s in tr["steps"] if s[1] != -1)),
+           "min_gap": None if worst["gap"] == float("inf") else worst["gap"]}
+    if prb:
+        rec.update(beta=float(ag.history.beta), total_priority=float(ag.history.tree.total_priority),
+                   len=len(ag.history), min_margin=worst["margin"])
+    series = {"actions": np.array([s[0] for s in tr["steps"]], dtype=np.int64),
+              "values": np.array([s[1] for s in tr["steps"]]), "eps": np.array([s[2] for s in tr["steps"]]),
+              "losses": np.array(tr["losses"])}
+    if prb:
+        series["per_idx"] = np.array(tr["per_idx"], dtype=np.int64)
+    return rec, init, final, series
+
+
+def gen_dqn(ref, out):
+    sessions, arrays = [], {}
+    for ci, cls_name in enumerate(DQN_CLASSES):
+        for eps_const in (None, 0.3):
+            seed = 10 * ci + (5 if eps_const else 0)
+            while True:
+                got = _dqn_session(cls_name, seed, eps_const)
+                if got is not None:
+                    break
+                seed += 100  # rejected: a near-tie between the two best legal Q values or at a tree threshold
+            rec, init, final, series = got
+            si = len(sessions)
+            for k, v in series.items():
+                arrays[f"s{si}_{k}"] = v
+            for k, v in init.items():
+                arrays[f"s{si}_init_{k}"] = v
+            for k, v in final.items():
+                arrays[f"s{si}_final_{k}"] = v
+            sessions.append(rec)
+    np.savez_compressed(os.path.join(out, "dqn_weights.npz"), **arrays)
+    with open(os.path.join(out, "dqn_games.json"), "w") as f:
+        json.dump({"protocol": "torch.manual_seed(seed); agent = <agent>(**kwargs[, eps_func = constant eps_const]); "
+                               "three DrunkHamster; agent.train(); np.random.seed(seed); random.seed(seed); "
+                               "GameSession(agent, hamsters...).play_game() x games.  dqn_weights.npz: s<i>_actions / _values / _eps = "
+                               "the move, info.value and info.eps of every forward, s<i>_losses = learn()[0] per "
+                               "step, s<i>_per_idx = the tree indices of every PER sample; here beta / total_priority / len = the replay at the end.  Seeds with a greedy "
+                               "decision whose two best legal Q values are within 1e-3 (min_gap), or a PER descent "
+                               "within 1e-6 x total of a threshold (min_margin; float32 priorities), were rejected.  Weights: "
+                               "dqn_weights.npz s<i>_init_* / s<i>_final_* (agent.state_dict()).  Python semantics of "
+                               "the PER sampler (numba.jit is a no-op here)",
+                   "sessions": sessions}, f)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests", "golden"))
@@ -965,6 +1188,8 @@ def main():
         ("acer", gen_acer),
         ("tournament", gen_tournament),
         ("evolve", gen_evolve),
+        ("per", gen_per),
+        ("dqn", gen_dqn),
     ]
     for name, fn in steps:
         if args.only and name not in args.only.split(","):
