@@ -189,13 +189,29 @@ sn_status sn_philox_counter(sn_env* env, int64_t game, uint64_t* counter_host);
                          group's twists nothing, so the default schedule
                          runs its ring dry (the SN_ERNG / sn_pipe_errors
                          path); 0 (default): off.
+     SN_OPT_TWIST_DEPTH  0 .. 3 (default 3): refill hysteresis of the whole-round
+                         twist-ahead (SN_OPT_TWIST_ROUND 1).  A game whose
+                         lead is at least the low threshold (600 K words,
+                         600 (K + 1) with decode-ahead) twists nothing in a
+                         k_mt_ahead dispatch; one below it twists whole rounds
+                         until the lead reaches the threshold + 624 depth.
+                         The rounds of a refill are chained in LDS, so the
+                         2 496-byte MT state is read and written once per
+                         refill instead of once per round, and the start-up
+                         twist staggers the games (+ 624 (game mod (depth +
+                         1)) words) so that they refill in different
+                         dispatches.  0 keeps the plain thresholds.  Same
+                         words, same outputs, same exported numpy states;
+                         the environment variable SECHS_TWIST_DEPTH
+                         overrides the default at sn_create.
    A pipelined (numpy-compat) rollout records its ordering event on the
    caller's stream before it returns; every later call waits on that event
    (also on the same stream), so the caller may destroy the stream after
    the call. */
 enum { SN_OPT_RING_WORDS = 1, SN_OPT_CHUNK_STEPS = 2, SN_OPT_PIPELINE = 3, SN_OPT_TIMING = 4, SN_OPT_PIPE_GPW = 5,
        SN_OPT_PIPE_LEAD = 6, SN_OPT_PLAY_SPLIT = 7, SN_OPT_PLAY_QUAD = 8, SN_OPT_TWIST_ROUND = 9,
-       SN_OPT_TWIST_EVERY = 10, SN_OPT_PIPE_FUSED = 11, SN_OPT_TWIST_SKIP = 12, SN_OPT_PIPE_DEC = 13 };
+       SN_OPT_TWIST_EVERY = 10, SN_OPT_PIPE_FUSED = 11, SN_OPT_TWIST_SKIP = 12, SN_OPT_PIPE_DEC = 13,
+       SN_OPT_TWIST_DEPTH = 14 };
 sn_status sn_set_option(sn_env* env, int option, int value);
 /* pipelined rollouts whose draws ran past the twisted words (must be 0; a
    nonzero count means those games' draws are wrong) [sync].  The count is

@@ -183,7 +183,7 @@ __global__ __launch_bounds__(kBlock) void k_mt_prep(DevState s) {
             if (k >= r && k < kt && k - r < D) {
                 v = mt_mix(A[q][b], bb, C[q][b]);
                 st[idx] = v;
-                if (idx == 0u) s.mt0[g] = A[q][b];
+                if (idx == 0u) s.mt0[g * kMt0Levels] = A[q][b];
             }
             if (b < NB) {  // ring bytes: 4 words per dword (lanes 4m..4m+3)
                 const uint32_t y = mt_temper(v) & 0xFFu;
@@ -203,7 +203,7 @@ __global__ __launch_bounds__(kBlock) void k_mt_prep(DevState s) {
                     const uint32_t a = st[idx];
                     v = mt_mix(a, st[(idx + 1u == (uint32_t)kMtN) ? 0u : idx + 1u], st[(idx < D) ? idx + kMtM : idx - D]);
                     st[idx] = v;
-                    if (idx == 0u) s.mt0[g] = a;
+                    if (idx == 0u) s.mt0[g * kMt0Levels] = a;
                 }
                 const uint32_t y = mt_temper(v) & 0xFFu;
                 const uint32_t d = y | (__shfl_down(y, 1) << 8) | (__shfl_down(y, 2) << 16) | (__shfl_down(y, 3) << 24);
@@ -265,20 +265,24 @@ struct AheadArgs {
     int lead;  // words to keep twisted past the consumer (kPipeLead; smaller only to test the overrun path)
     uint32_t* perr_mirror;  // host-mapped copy of *perr, refreshed at launch start (off the play stream)
     int cin_copy;  // INIT: also write the start position to this pabsc slot (-1: none; decode-ahead: the play slot)
+    int depth;     // ROUND: whole rounds a refilling game twists past `lead` (SN_OPT_TWIST_DEPTH, 0 .. kTwistDepthMax)
 };
 
 // One whole MT19937 round of game G, twisted by the whole wave in LDS (w:
-// 624 words; k_mt_ahead's whole-round twists), its
-// tempered low bytes to the ring at stream positions te .. te + 623 (te is
-// 8-aligned: rounds are 624 = 78 x 8 words).  numpy's in-place order in
-// three dependency-free phases: words 0..226 read old words only (mt[i+1],
-// mt[i+397]); 227..453 read old mt[i+1] and the new mt[i-227] of phase 1;
-// 454..623 the new mt[i-227] of phase 2 (and mt[623] the new mt[0]).  One
-// HBM read and one write per word (k_mt_ahead's partial twists read the
-// i+397 input a second time).  Returns the old mt[0] (the one word the
-// sync-time untwist cannot recover, mt0).
-// v: the round's old words (word 64k + lane in v[k]), loaded by the caller
-// (a round ahead: mt_round_load)
+// 624 words; k_mt_ahead's whole-round twists), in three pieces: the state is
+// loaded once (mt_round_load, mt_round_to_lds), then every round of a refill
+// is twisted in place in LDS (mt_twist_lds) and its tempered low bytes go to
+// the ring at stream positions te .. te + 623 (mt_round_emit; te is
+// 8-aligned: rounds are 624 = 78 x 8 words), and the state goes back to HBM
+// once, after the refill's last round (mt_round_store) -- one HBM read and
+// one write of the state per REFILL, however many rounds it chains, plus one
+// ring byte per word.  numpy's in-place order in three dependency-free
+// phases: words 0..226 read old words only (mt[i+1], mt[i+397]); 227..453
+// read old mt[i+1] and the new mt[i-227] of phase 1; 454..623 the new
+// mt[i-227] of phase 2 (and mt[623] the new mt[0]).  (k_mt_ahead's partial
+// twists read the i+397 input a second time.)  mt_twist_lds returns the old
+// mt[0] (the one word the sync-time untwist cannot recover, mt0).
+// v: the state's words (word 64k + lane in v[k])
 __device__ __forceinline__ void mt_round_load(const DevState& s, int64_t G, uint32_t lane, uint32_t (&v)[10]) {
     const uint32_t* st = s.mt + G * kMtN;
 #pragma unroll
@@ -298,10 +302,8 @@ __device__ __forceinline__ void mt_round_to_lds(uint32_t lane, uint32_t* w, cons
 }
 
 // w holds the round's old words (mt_round_to_lds)
-__device__ __forceinline__ uint32_t mt_twist_round(const DevState& s, int64_t G, uint32_t lane, uint32_t* w,
-                                                     uint32_t te) {
+__device__ __forceinline__ uint32_t mt_twist_lds(uint32_t lane, uint32_t* w) {
     constexpr uint32_t D = kMtN - kMtM;  // 227
-    uint32_t* st = s.mt + G * kMtN;
     const uint32_t old0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)w[0]);
     uint32_t nv[4];
 #pragma unroll
@@ -340,13 +342,13 @@ __device__ __forceinline__ uint32_t mt_twist_round(const DevState& s, int64_t G,
         if (i < (uint32_t)kMtN) w[i] = nv[k];
     }
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    // the new round to HBM (state words), its tempered low bytes to the ring
-    // (4 per dword: dword d holds stream positions te + 4d .. te + 4d + 3)
-#pragma unroll
-    for (int k = 0; k < 10; k++) {
-        const uint32_t i = 64u * k + lane;
-        if (i < (uint32_t)kMtN) st_nt(&st[i], w[i], SECHS_NT_MORE);
-    }
+    return old0;
+}
+
+// the tempered low bytes of the round in w to the ring (4 per dword: dword d
+// holds stream positions te + 4d .. te + 4d + 3)
+__device__ __forceinline__ void mt_round_emit(const DevState& s, int64_t G, uint32_t lane, const uint32_t* w,
+                                              uint32_t te) {
     uint8_t* ring = (uint8_t*)s.pring;
 #pragma unroll
     for (int k = 0; k < 3; k++) {
@@ -359,20 +361,36 @@ __device__ __forceinline__ uint32_t mt_twist_round(const DevState& s, int64_t G,
             st_nt((uint32_t*)(ring + ring_byte(ri, G, s.B)), y, SECHS_NT_MORE);  // ri is 4-aligned
         }
     }
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");  // the LDS reads before the next round's writes
+}
+
+// the state in w back to HBM (after the last round of a refill)
+__device__ __forceinline__ void mt_round_store(const DevState& s, int64_t G, uint32_t lane, const uint32_t* w) {
+    uint32_t* st = s.mt + G * kMtN;
+#pragma unroll
+    for (int k = 0; k < 10; k++) {
+        const uint32_t i = 64u * k + lane;
+        if (i < (uint32_t)kMtN) st_nt(&st[i], w[i], SECHS_NT_MORE);
+    }
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");  // the LDS reads before the area's next use
-    return old0;
 }
 
 // ROUND (SN_OPT_TWIST_ROUND): twist whole MT rounds instead of exactly the
 // words the lead needs.  A twist that is due first completes the current
-// round (the per-64-word form below), then -- if the lead is still short --
-// twists the next round of 624 words in LDS: the round's old words are read
-// once, every input of numpy's in-place order (mt[i+1], mt[i+397] / the new
-// mt[i-227]) comes from LDS, and each new word is written once: 8 B of MT
-// traffic per word instead of 12 (the X input of a partial twist is a
-// second HBM read).  The lead then ranges up to 600 + 624 words, so the
-// ring holds kPipeRing = 2048 bytes per game; a handle synchronised while
-// the array is a round ahead of its consumer is untwisted (k_pipe_code).
+// round (the per-64-word form below, at start-up only: afterwards the twist
+// pointer rests on a round boundary), then -- if the lead is still short --
+// twists whole rounds of 624 words in LDS: the state is read once, every
+// input of numpy's in-place order (mt[i+1], mt[i+397] / the new mt[i-227])
+// comes from LDS, and the state is written once after the last round.
+// Refill with hysteresis (SN_OPT_TWIST_DEPTH = a.depth): a game whose lead
+// is at least a.lead twists nothing in this dispatch; one below it twists
+// until the lead reaches a.lead + 624 depth, so the 2 x 2 496 B of state
+// traffic are shared by depth + 1 rounds and most games skip most
+// dispatches.  INIT staggers the games (lead a.lead + 624 (g mod (depth +
+// 1))) so that they do not all refill in the same dispatch.  The lead ranges
+// up to kPipeSpanMax words (sechs_state.h), which the ring of kPipeRing =
+// 8192 bytes per game holds; a handle synchronised while the array is rounds
+// ahead of its consumer is untwisted (k_pipe_code, up to kMt0Levels rounds).
 template <bool INIT, bool ROUND = false>
 __global__ __launch_bounds__(kBlock) void k_mt_ahead(DevState s, AheadArgs a) {
     constexpr uint32_t D = kMtN - kMtM;  // 227
@@ -417,8 +435,12 @@ __global__ __launch_bounds__(kBlock) void k_mt_ahead(DevState s, AheadArgs a) {
     const int32_t lead = (int32_t)(t0 - c);
     if (lead < 0 && lane == 0u) atomicAdd(s.perr, 1u);
     const uint32_t T0 = (Tp == (uint32_t)kMtN) ? 0u : Tp;
+    // ROUND: a game refills when its lead is below lo, up to hi (the hysteresis; INIT: the staggered start-up lead)
+    const int32_t lo = a.lead + ((ROUND && INIT) ? kMtN * (int32_t)(g % (int64_t)(a.depth + 1)) : 0);
+    const int32_t hi = (ROUND && !INIT) ? a.lead + kMtN * a.depth : lo;
+    const bool refill = lead >= 0 && lead < lo;
     // ROUND: the words completing the current round (none at a round boundary)
-    const uint32_t n = ROUND ? ((lead >= 0 && lead < a.lead && T0 != 0u) ? (uint32_t)kMtN - T0 : 0u)
+    const uint32_t n = ROUND ? ((refill && T0 != 0u) ? (uint32_t)kMtN - T0 : 0u)
                              : ((lead >= 0 && lead < a.lead) ? (((uint32_t)(a.lead - lead)) & ~7u) : 0u);
     auto ring_dword = [&](uint32_t j, uint32_t v) {  // t0 is 8-aligned: lanes 4m..4m+3 share one dword
         const uint32_t y = mt_temper(v) & 0xFFu;
@@ -429,16 +451,15 @@ __global__ __launch_bounds__(kBlock) void k_mt_ahead(DevState s, AheadArgs a) {
     // Word-0 crossings of this launch (wave-uniform count): the overwritten
     // old mt[0] of each.  k_pipe_code's untwist needs one per round the array
     // runs ahead of the consumer -- up to three with SN_OPT_TWIST_EVERY = 3
-    // (a lead of 1 800 words) -- so mt0[k B + g] keeps the k-th newest; kept
-    // in registers here, so no load follows a store of this launch.
-    uint32_t ncross = 0u, old0[kMt0Levels] = {};
+    // (a lead of 1 800 words) -- so mt0[g][k] keeps the k-th newest; kept
+    // in a register here (lane k: the k-th), so no load follows a store of this launch.
+    uint32_t ncross = 0u, old0 = 0u;  // lane k: this launch's k-th newest crossing
     auto cross = [&](bool hit, uint32_t old) {
         const uint64_t m = __ballot(hit);
         if (m) {
             const uint32_t v = __shfl(old, (int)__builtin_ctzll(m));
-#pragma unroll
-            for (int k = kMt0Levels - 1; k > 0; k--) old0[k] = old0[k - 1];  // newest first
-            old0[0] = v;
+            const uint32_t up = __shfl_up(old0, 1);  // newest first
+            old0 = lane ? up : v;
             ncross++;
         }
     };
@@ -489,30 +510,39 @@ __global__ __launch_bounds__(kBlock) void k_mt_ahead(DevState s, AheadArgs a) {
         while (Tn > (uint32_t)kMtN) Tn -= kMtN;
     }
     if constexpr (ROUND) {
-        // whole rounds in LDS while the lead is short (one per twist at K <= 2, up to kMt0Levels - 1)
-        for (int rr = 0; rr < kMt0Levels - 1 && lead >= 0 && lead + (int32_t)(te - t0) < a.lead; rr++) {
+        // whole rounds, chained in the wave's LDS area, until the lead reaches hi (at most kMt0Levels - 1:
+        // the start-up lead is fewer, sechs_state.h): one state load before, one state store after
+        if (refill && lead + (int32_t)(te - t0) < hi) {
             __shared__ __attribute__((aligned(16))) uint32_t wround[kBlock / 64][kMtN];
             uint32_t* w = wround[threadIdx.x >> 6];
             __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");  // the words twisted before: stored first
             uint32_t v[10];
             mt_round_load(s, g, lane, v);  // all ten loads in flight at once
             mt_round_to_lds(lane, w, v);
-            // three dependency-free phases (mt_twist_round); old mt[0]: the one word the untwist cannot recover
-            cross(true, mt_twist_round(s, g, lane, w, te));
-            te += kMtN;
+            for (int rr = 0; rr < kMt0Levels - 1 && lead + (int32_t)(te - t0) < hi; rr++) {
+                // three dependency-free phases; old mt[0]: the one word the untwist cannot recover
+                cross(true, mt_twist_lds(lane, w));
+                mt_round_emit(s, g, lane, w, te);
+                te += kMtN;
+            }
+            mt_round_store(s, g, lane, w);
             Tn = kMtN;
         }
     }
     SN_DASSERT(ncross <= (uint32_t)kMt0Levels);
+    // the span the ring holds: the twisted end leads the consumer followed by at most kPipeSpanMax words
+    // (a lowered test lead included), and a game that did not refill had the low threshold already
+    SN_DASSERT(lead < 0 || te - c <= (uint32_t)kPipeSpanMax);
+    SN_DASSERT(!ROUND || lead < 0 || te == t0 || (int32_t)(te - c) >= hi);
+    SN_DASSERT(!ROUND || te == t0 || Tn == (uint32_t)kMtN);
     if (lane == 0u) {
         s.ptp[g] = Tn;
         s.ptend[(int64_t)a.tout * B + g] = te;
-        if (ncross) {  // the stack of crossings, newest first: this launch's, then the older ones
-            uint32_t stk[kMt0Levels];
-            for (int k = 0; k < kMt0Levels; k++) stk[k] = s.mt0[k * B + g];
-            for (int k = 0; k < kMt0Levels; k++)
-                s.mt0[k * B + g] = (k < (int)ncross) ? old0[k] : stk[k - (int)ncross];
-        }
+    }
+    if (ncross) {  // the stack of crossings, newest first: this launch's, then the older ones (one 64-B line)
+        const uint32_t stk = (lane < (uint32_t)kMt0Levels) ? s.mt0[g * kMt0Levels + lane] : 0u;
+        const uint32_t older = __shfl(stk, (int)((lane - ncross) & 63u));
+        if (lane < (uint32_t)kMt0Levels) s.mt0[g * kMt0Levels + lane] = (lane < ncross) ? old0 : older;
     }
 }
 
@@ -561,7 +591,7 @@ __global__ __launch_bounds__(kBlock) void k_pipe_code(DevState s, int cin, int t
             y[j] = mt_untwist_y_dev(w[j] ^ old_k);
         }
         __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-        const uint32_t m0 = s.mt0[lvl * s.B + g];
+        const uint32_t m0 = s.mt0[g * kMt0Levels + lvl];
         for (uint32_t j = lane; j < tp; j += 64u)
             w[j] = (y[j] & 0x80000000u) | ((j ? y[j - 1u] : m0) & 0x7fffffffu);
         __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
@@ -570,9 +600,12 @@ __global__ __launch_bounds__(kBlock) void k_pipe_code(DevState s, int cin, int t
     }
     if (lvl) {
         for (uint32_t j = lane; j < (uint32_t)kMtN; j += 64u) a[j] = w[j];
-        if (lane == 0u)
-            for (int k = 0; k < kMt0Levels; k++)  // the crossings not undone are the newest now
-                s.mt0[k * s.B + g] = (k + lvl < kMt0Levels) ? s.mt0[(k + lvl) * s.B + g] : 0u;
+        if (lane < (uint32_t)kMt0Levels) {  // the crossings not undone are the newest now (lane k: level k)
+            const uint32_t k = lane + (uint32_t)lvl;
+            const uint32_t v = (k < (uint32_t)kMt0Levels) ? s.mt0[g * kMt0Levels + k] : 0u;
+            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");  // every lane's load before any store
+            s.mt0[g * kMt0Levels + lane] = v;
+        }
     }
     SN_DASSERT(rem <= kMtN);
     if (lane == 0u) s.mt_pos[g] = tp | ((uint32_t)max(rem, 0) << 16);
@@ -1668,7 +1701,7 @@ sn_status sn_create(sn_env** out, int device, int64_t num_games, int num_players
         {(void**)&s.sum_res, sizeof(int32_t) * N * B},     {(void**)&s.episodes, sizeof(int32_t) * B},
         {(void**)&s.mt_pos, sizeof(uint32_t) * B},         {(void**)&s.ctr, sizeof(uint64_t) * B},
         {(void**)&s.mt, rng_mode == SN_RNG_NUMPY_MT ? sizeof(uint32_t) * kMtN * B : 4},
-        {(void**)&s.mt0, sizeof(uint32_t) * kMt0Levels * B},  // [0]: newest crossing, then the ones before
+        {(void**)&s.mt0, sizeof(uint32_t) * kMt0Levels * B},  // per game: [0] newest crossing, then the ones before
     };
     for (auto& a : allocs) {
         if (hipMalloc(a.p, a.bytes) != hipSuccess) {
@@ -1690,7 +1723,12 @@ sn_status sn_create(sn_env** out, int device, int64_t num_games, int num_players
     e->twist_every = 4;
     {
         const char* te = getenv("SECHS_TWIST_EVERY");  // default override (A/B runs of whole legs)
-        if (te && atoi(te) >= 1 && atoi(te) <= 5) e->twist_every = atoi(te);
+        if (te && atoi(te) >= 1 && atoi(te) <= kTwistEveryMax) e->twist_every = atoi(te);
+    }
+    e->twist_depth = 3;  // measured: the fastest of 0 .. 3 on both bench commands
+    {
+        const char* td = getenv("SECHS_TWIST_DEPTH");  // default override (A/B runs of whole legs)
+        if (td && td[0] >= '0' && td[0] <= '0' + kTwistDepthMax && !td[1]) e->twist_depth = td[0] - '0';
     }
     {
         const char* ps = getenv("SECHS_PIPE_SERIAL");
@@ -1838,8 +1876,12 @@ sn_status sn_set_option(sn_env* e, int option, int value) {
             e->play_split = value;
             return SN_OK;
         case SN_OPT_TWIST_EVERY:
-            if (value < 1 || value > 5) return fail(SN_EINVAL, "twist every must be 1 .. 5");
+            if (value < 1 || value > kTwistEveryMax) return fail(SN_EINVAL, "twist every must be 1 .. 5");
             e->twist_every = value;
+            return SN_OK;
+        case SN_OPT_TWIST_DEPTH:  // thresholds only: takes effect at the next twist, no pipeline restart
+            if (value < 0 || value > kTwistDepthMax) return fail(SN_EINVAL, "twist depth must be 0 .. 3");
+            e->twist_depth = value;
             return SN_OK;
         case SN_OPT_TWIST_ROUND:
             if (value < 0 || value > 1) return fail(SN_EINVAL, "twist round must be 0 or 1");
@@ -2146,8 +2188,9 @@ static sn_status launch_pipe(sn_env* e, PlayArgs a, hipStream_t st) {
     // Slots: pabsc by launch index mod kPipeSlots (8 >= K + 3: the next writer
     // of launch p-1's slot is launch p+7, in group G+1 or later, which is
     // ordered behind twist G -- the reader of that slot), ptend by group
-    // parity (INIT = launch -1 / twist -1).  The ring holds the lead + a round
-    // for K <= 5 (3 623 words), and mt0 the five word-0 crossings that span.
+    // parity (INIT = launch -1 / twist -1).  The ring holds the lead, the
+    // SN_OPT_TWIST_DEPTH rounds a refill adds and a round's overshoot for K <= 5
+    // (kPipeSpanMax, sechs_state.h), and mt0 the word-0 crossings of that span.
     const int K = e->twist_every;
     const bool round_tw = e->twist_round;
     if (e->pvalid && (e->pK != K || (e->pdec != 0) != dec)) {  // restart with the other group size / form
@@ -2157,14 +2200,15 @@ static sn_status launch_pipe(sn_env* e, PlayArgs a, hipStream_t st) {
     // Decode-ahead: twist G runs on `side` CONCURRENTLY with decode G on `side2`, so it leads
     // the decoder position after decode G-1 (slot kDecSlot + ((G - 1) & 1)) by the words of
     // the 2K + 1 episodes decode G+1 may need: 600 (K + 1) words (~200 per episode at N <= 4;
-    // the ring holds the lead + a round up to 3 472), and the play launches read no ring at
+    // the ring holds the lead + the refill depth + a round, kPipeSpanMax), and the play launches read no ring at
     // all.  Otherwise the twists lead the play consumer by 600 K words.
     const int lead = dec ? min(e->pipe_lead * (K + 1), kPipeRing - kMtN) : e->pipe_lead * K;
+    static_assert(kPipeLeadMax <= kPipeRing - kMtN, "the decode-ahead lead is never capped by the ring");
     constexpr uint32_t kSlotMask = (uint32_t)kPipeSlots - 1u;
     if (!e->pvalid) {  // start the pipeline from mt_pos: twist the lead ahead, synchronously
         // decode-ahead: the start position to the decoder's input slot of the first decode and
         // the play slot (a sync before any play launch exports it)
-        const AheadArgs aa{dec ? kDecSlot : (int)kSlotMask, 0, 1, lead, e->perr_host_dev, dec ? (int)kSlotMask : -1};
+        const AheadArgs aa{dec ? kDecSlot : (int)kSlotMask, 0, 1, lead, e->perr_host_dev, dec ? (int)kSlotMask : -1, e->twist_depth};
         e->tw_out = 1, e->pl_cout = (int)kSlotMask, e->pphase = 0;
         if (round_tw) hipLaunchKernelGGL((k_mt_ahead<true, true>), pg, dim3(kBlock), 0, st, s, aa);
         else hipLaunchKernelGGL((k_mt_ahead<true, false>), pg, dim3(kBlock), 0, st, s, aa);
@@ -2234,7 +2278,7 @@ static sn_status launch_pipe(sn_env* e, PlayArgs a, hipStream_t st) {
             if (tv) HIP_TRY(hipEventRecord(tv[2], e->side));
             // SN_OPT_TWIST_SKIP (tests only): the overrun detector under the default schedule
             const AheadArgs aa{dec ? kDecSlot + (int)((G + 1u) & 1u) : c.pipe_cin, c.pipe_t, (int)(G & 1u),
-                               (e->twist_skip && G >= 1u) ? 0 : lead, e->perr_host_dev, -1};
+                               (e->twist_skip && G >= 1u) ? 0 : lead, e->perr_host_dev, -1, e->twist_depth};
             if (round_tw) hipLaunchKernelGGL((k_mt_ahead<false, true>), pg, dim3(kBlock), 0, e->side, s, aa);
             else hipLaunchKernelGGL((k_mt_ahead<false, false>), pg, dim3(kBlock), 0, e->side, s, aa);
             HIP_TRY(hipGetLastError());
@@ -2559,7 +2603,7 @@ sn_status sn_mt_get(sn_env* e, int64_t game, uint32_t* key, int32_t* pos) {
     const int p = (int)(code & 0x7FFu), cnt = (int)((code >> 16) & kMtCntMask);
     if (cnt > p && p > 0) {  // straddling: still in the previous round, whose head [0, p) was overwritten
         uint32_t old0 = 0;
-        HIP_TRY(hipMemcpy(&old0, e->s.mt0 + game, sizeof(uint32_t), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(&old0, e->s.mt0 + game * kMt0Levels, sizeof(uint32_t), hipMemcpyDeviceToHost));
         mt_unstraddle(key, p, old0);
     } else if (p > 0 && p < kMtN) {
         mt_finish_round(key, p);  // twist the rest of this round in place

@@ -201,7 +201,7 @@ __global__ __launch_bounds__(64) void k_league_mcs(DevState s, LeagueStepArgs a)
         }
         if (lane == 0u) s.lpc[g * N + p] = (int32_t)card;
     }
-    wmt_store(m, s.mt + g * kMtN, s.mt_pos + g, s.mt0 + g, lane);
+    wmt_store(m, s.mt + g * kMtN, s.mt_pos + g, s.mt0 + g * kMt0Levels, lane);
     if (lane == 0u) s.lpf[g] = 1 | (q6s << 1);
 }
 

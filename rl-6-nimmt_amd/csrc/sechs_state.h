@@ -38,8 +38,8 @@ struct DevState {
     uint32_t* mt;
     uint32_t* mt_pos;
     uint64_t* ctr;
-    uint32_t* mt0;   // [kMt0Levels][B] old-round mt[0] of the newest word-0 crossing (export of straddling
-                     // codes), then the crossings before it (k_mt_ahead / k_pipe_code untwist, several rounds)
+    uint32_t* mt0;   // [B][kMt0Levels] per game (one 64-B line): old-round mt[0] of the newest word-0 crossing (export
+                     // of straddling codes), then the crossings before it (k_mt_ahead / k_pipe_code untwist, several rounds)
     u32x4* ring;     // [ring_w/16][B] low bytes of the words k_mt_prep twisted ahead
     int ring_w;      // ring words per game (multiple of 64), 0 = no ring
     int pad2_;
@@ -60,13 +60,14 @@ struct DevState {
     int32_t* lpf;    // [B] 1 (| 2: quirk Q6): lpc holds this step's non-external cards
 };
 
-constexpr int kMt0Levels = 8;    // word-0 crossings kept in mt0 (the decode-ahead span: up to seven rounds)
+constexpr int kMt0Levels = 16;   // word-0 crossings kept in mt0: the rounds the state array may lead the play
+                                 // consumer at a sync (derived and asserted below, at kPipeSpanMax)
 constexpr int kPipeSlots = 8;    // pabsc buffers (by play launch index mod 8; ptend uses 2, by twist parity)
 constexpr int kDecSlot = kPipeSlots;  // pabsc slots kDecSlot + (G & 1): the decoder's position after decode G
 constexpr int kDecRecords = 16;  // decode-ahead record ring (episodes; >= 2K + 2 for K <= 5)
 constexpr int kDecQuads = 6;     // 16-B pieces per record (24 dwords, the layout at DecSrc)
 constexpr int kTimingEvents = 6; // SN_OPT_TIMING events per launch: play, twist, decode (start, end)
-constexpr int kPipeRing = 4096;  // ring bytes per game (>= the lead 600 K + a whole round's overshoot: 3 623 at K = 5)
+constexpr int kPipeRing = 8192;  // ring bytes per game (a power of two >= kPipeSpanMax + a 64-B chunk, below)
 
 // pring layout: 64-byte chunks interleaved over games -- stream positions
 // 64 c .. 64 c + 63 of game g at chunk c * B + g -- so a twist wave's
@@ -86,6 +87,33 @@ __host__ __device__ __forceinline__ int64_t ring_byte(uint32_t ri, int64_t g, in
 constexpr int kPipeWin = 240;    // of them, copied to LDS per lane at a k_play launch: a 4-player
                                   // episode draws 193.5 words, P(> 240) = 7e-6 per game (the rest come
                                   // from HBM); 304 -> 240 measured 7.46 -> 7.60 G env-steps/s interleaved
+
+// Capacity of the twist-ahead (k_mt_ahead, ROUND mode).  A game refills when
+// its lead over the consumer it follows (the decoder with decode-ahead, else
+// the play launch before the running one) is below the low threshold `lead`
+// = 600 (K + 1) resp. 600 K words, and then twists whole rounds until the
+// lead reaches lead + 624 depth (SN_OPT_TWIST_DEPTH; the start-up twist:
+// lead + 624 (g mod (depth + 1))), overshooting by at most a round less one
+// word.  The twisted end therefore never leads that consumer by more than
+constexpr int kTwistEveryMax = 5, kTwistDepthMax = 3;
+constexpr int kPipeLeadMax = kPipeLead * (kTwistEveryMax + 1);                    // 3 600 (decode-ahead, K = 5)
+constexpr int kPipeSpanMax = kPipeLeadMax + kMtN * kTwistDepthMax + kMtN - 1;     // 6 095 words
+// and the ring, which a consumer reads from the 16-B unit holding its
+// position on, holds that span plus a 64-B chunk of slack:
+static_assert(kPipeSpanMax + 64 <= kPipeRing && (kPipeRing & (kPipeRing - 1)) == 0, "pring holds the twisted span");
+// At a sync k_pipe_code untwists the state array back to the PLAY consumer's
+// round.  With decode-ahead the decoder that twist G followed (decode G-1)
+// had decoded at most the 2K + 1 episodes from the one the play consumer is
+// in (launch_pipe's target) -- at most 296 words each, the launch-pair tail
+// bound of pipe_max_chunk (592 words per two episodes at N <= 4) -- so the
+// unconsumed words are at most
+constexpr int kPipeSyncSpanMax = 296 * (2 * kTwistEveryMax + 1) + kPipeSpanMax;  // 9 351 words
+// of which one round stays twisted: the rest, in whole rounds, is undone with one mt0 level each.
+static_assert((kPipeSyncSpanMax - kMtN + kMtN - 1) / kMtN <= kMt0Levels, "mt0 holds every round k_pipe_code may undo");
+// (Without decode-ahead the play consumer is the one followed: kPipeSpanMax at
+// most.)  One dispatch twists at most the start-up's rounds: that span, one
+// crossing per round.
+static_assert((kPipeSpanMax + kMtN - 1) / kMtN < kMt0Levels, "k_mt_ahead's round loop reaches the start-up lead");
 
 constexpr int kBlock = 256;
 constexpr int kLeagueMaxPlayers = 6;  // tournament handles: 2..6 seats (agent ids packed 4 bits per seat)
@@ -199,7 +227,7 @@ struct RingGen {
         rb = (uint32_t)s.ring_w;  // k_mt_prep left rem >= ring_w
         extra = rem - rb;
         st = s.mt + g * kMtN;
-        mt0 = s.mt0 + g;
+        mt0 = s.mt0 + g * kMt0Levels;
         B = s.B;
         base = s.ring + g;
         nq = rb >> 4;
@@ -356,73 +384,6 @@ struct RingPipe {
         const PipeSlow r = pipe_slow(ring, B, g, c0 + take, left, err);
         buf.append(r.bytes, r.k);
         take += r.k;
-        return true;
-    }
-    __device__ __forceinline__ void topup(ByteBuf& buf) {
-        if (buf.cnt <= 24u) gen(buf, false);
-    }
-    __device__ __forceinline__ void force(ByteBuf& buf) { gen(buf, true); }
-};
-
-// The pipelined ring read straight from HBM (k_decode, the decode-ahead
-// producer): the next 8 bytes at any stream position from two 16-B units
-// held in registers (the one holding the position and the next, loaded one
-// unit ahead), the same words RingPipe hands out.  A top-up never reads past
-// the twisted end; a draw that needs a word past it counts an overrun (perr,
-// sticky) and takes zero bytes, as pipe_slow.
-struct RingDirect {
-    static constexpr int kAhead = 4;  // 16-B units in flight past the one being read (~64 words of draws)
-    const u32x4* ring;
-    uint32_t* err;
-    int64_t B, g;
-    uint32_t pos;  // stream position of the next byte not yet appended
-    uint32_t end;  // twisted end (ptend)
-    uint32_t unit;  // pos >> 4 (the unit `cur` holds)
-    u32x4 cur, nx[kAhead];  // units unit, unit + 1 .. unit + kAhead (a register queue: static indices only)
-
-    __device__ __forceinline__ void load(const DevState& s, int64_t gg, uint32_t c, uint32_t tend, ByteBuf& buf) {
-        ring = s.pring, err = s.perr, B = s.B, g = gg;
-        pos = c, end = tend, unit = c >> 4;
-        cur = ring[ring16(unit, g, B)];
-#pragma unroll
-        for (int k = 0; k < kAhead; k++) nx[k] = ring[ring16(unit + 1u + (uint32_t)k, g, B)];
-        buf.clear();
-    }
-    __device__ __forceinline__ uint32_t consumed(const ByteBuf& buf) const { return pos - buf.cnt; }
-    __device__ __forceinline__ uint64_t peek8() const {
-        const uint32_t off = pos & 15u, sh = 8u * (off & 7u);
-        const uint64_t q0 = (uint64_t)cur.x | ((uint64_t)cur.y << 32), q1 = (uint64_t)cur.z | ((uint64_t)cur.w << 32);
-        const uint64_t q2 = (uint64_t)nx[0].x | ((uint64_t)nx[0].y << 32);
-        const uint64_t lo = (off >= 8u) ? q1 : q0, hi = (off >= 8u) ? q2 : q1;
-        return sh ? ((lo >> sh) | (hi << (64u - sh))) : lo;
-    }
-    __device__ __forceinline__ void advance(uint32_t k) {
-        pos += k;
-        const uint32_t u = pos >> 4;  // (positions wrap at 2^32: a start-up consumer sits just below 0)
-        if (u != unit) {              // at most one unit per call (k <= 8)
-            unit = u;
-            cur = nx[0];
-#pragma unroll
-            for (int q = 0; q + 1 < kAhead; q++) nx[q] = nx[q + 1];
-            nx[kAhead - 1] = ring[ring16(unit + (uint32_t)kAhead, g, B)];
-        }
-    }
-    // forced = the buffer is empty and a draw needs a word now
-    __device__ __forceinline__ bool gen(ByteBuf& buf, bool forced) {
-        const uint32_t left = ((int32_t)(end - pos) > 0) ? end - pos : 0u;
-        if (left >= 8u) {
-            buf.append(peek8(), 8u);
-            advance(8u);
-            return true;
-        }
-        if (left == 0u) {
-            if (!forced) return false;  // prefetch stops at the twisted end
-            atomicAdd(err, 1u);         // an overrun: the stream is lost, draw zeros
-            buf.append(0ull, 8u);
-            return true;
-        }
-        buf.append(peek8(), left);
-        advance(left);
         return true;
     }
     __device__ __forceinline__ void topup(ByteBuf& buf) {
@@ -960,6 +921,7 @@ struct sn_env {
     int pK;           // SN_OPT_TWIST_EVERY of the running pipeline
     hipEvent_t evt[2];  // after twist G, slot G mod 2
     int twist_skip;   // SN_OPT_TWIST_SKIP (tests only): steady twists after the first group twist nothing
+    int twist_depth;  // SN_OPT_TWIST_DEPTH: extra whole rounds a refilling game twists past the lead (0 .. kTwistDepthMax)
     int pipe_dec;     // SN_OPT_PIPE_DEC: decode-ahead (k_decode + k_play<RNG_NUMPY_DEC>) where it applies
     int pdec;         // the running pipeline decodes ahead
     int64_t dec_e;    // decode-ahead: episodes the play launches finished since the pipeline start
