@@ -101,6 +101,10 @@ sn_status sn_step(sn_env* env, const int32_t* actions, int32_t* rewards, uint8_t
      actions [steps][B][N] uint8,
      obs     [steps][B][N][obs_stride] int8: the observation each seat acts
              on (env.py:174-212, pre-action), zero-padded to obs_stride >= L.
+             obs_stride is a multiple of 4 and obs 4-byte aligned; rows of
+             obs_stride == 48 leave as 16-byte pieces, so such an obs must be
+             16-byte aligned.  A violation is SN_EINVAL before anything is
+             launched or any handle state changes.
    flags: SN_AUTO_RESET (required when steps run past a game's end),
           SN_NO_SUMMARIES. */
 sn_status sn_rollout(sn_env* env, int steps, int32_t* rewards, uint8_t* done, uint8_t* actions, int8_t* obs,

@@ -1666,6 +1666,33 @@ sn_status set_error(sn_status st, const std::string& msg) {
 
 static sn_status fail(sn_status st, const std::string& msg) { return set_error(st, msg); }
 
+// launch templates (C++ linkage: ahead of the C ABI block)
+// One k_play launch.  The instantiations that exist: league seats for 2 .. 6 players, decode-ahead for N <= 4
+// (no handle reaches the others: sn_league_config, dec_ok).
+template <int NN, int MODE, int GPW = 64, bool LG = false>
+static sn_status launch_k_play(const DevState& s, const PlayArgs& a, unsigned grid, size_t shmem, hipStream_t st) {
+    if constexpr ((!LG || (NN >= 2 && NN <= kLeagueMaxPlayers)) && (MODE != RNG_NUMPY_DEC || NN <= kSplitMaxPlayers)) {
+        HIP_TRY(hipFuncSetAttribute((const void*)k_play<NN, MODE, GPW, LG>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
+        hipLaunchKernelGGL((k_play<NN, MODE, GPW, LG>), dim3(grid), dim3(kBlock), shmem, st, s, a);
+        HIP_TRY(hipGetLastError());
+    }
+    return SN_OK;
+}
+
+// k_mt_prep<ring_w / 64> for the ring sizes sn_set_option admits (64 .. 512 words)
+template <int NB = 1>
+static sn_status launch_mt_prep(const DevState& s, hipStream_t st) {
+    if constexpr (NB <= 8) {
+        if (s.ring_w / 64 != NB) return launch_mt_prep<NB + 1>(s, st);
+        constexpr int GPW = kPrepGamesPerWave;
+        const dim3 pg((unsigned)((s.B + GPW * (kBlock / 64) - 1) / (GPW * (kBlock / 64))));
+        hipLaunchKernelGGL((k_mt_prep<NB, GPW>), pg, dim3(kBlock), 0, st, s);
+        return SN_OK;
+    } else {
+        return fail(SN_EINVAL, "bad ring size");
+    }
+}
+
 extern "C" {
 
 const char* sn_last_error(void) { return g_err.c_str(); }
@@ -1710,37 +1737,35 @@ sn_status sn_create(sn_env** out, int device, int64_t num_games, int num_players
         }
         (void)hipMemset(*a.p, 0, a.bytes);
     }
-    e->chunk_steps = 10;
-    e->pipe = 1;
-    e->pipe_gpw = 64;
-    e->pipe_lead = kPipeLead;
+    e->opt.chunk_steps = 10;
+    e->opt.pipe = 1;
+    e->opt.pipe_gpw = 64;
+    e->opt.pipe_lead = kPipeLead;
     e->phase = -1;
-    e->play_split = 1;
+    e->opt.play_split = 1;
     // measured: three-phase whole-round twists, the
     // ring in 64-B chunks and one twist per four play launches: 0.0861 ->
     // 0.0775 ms per step same box (K = 1 -> 4; K = 2: 0.0792, 3: 0.0783)
-    e->twist_round = 1;
-    e->twist_every = 4;
+    e->opt.twist_round = 1;
+    e->opt.twist_every = 4;
     {
         const char* te = getenv("SECHS_TWIST_EVERY");  // default override (A/B runs of whole legs)
-        if (te && atoi(te) >= 1 && atoi(te) <= kTwistEveryMax) e->twist_every = atoi(te);
+        if (te && atoi(te) >= 1 && atoi(te) <= kTwistEveryMax) e->opt.twist_every = atoi(te);
     }
-    e->twist_depth = 3;  // measured: the fastest of 0 .. 3 on both bench commands
+    e->opt.twist_depth = 3;  // measured: the fastest of 0 .. 3 on both bench commands
     {
         const char* td = getenv("SECHS_TWIST_DEPTH");  // default override (A/B runs of whole legs)
-        if (td && td[0] >= '0' && td[0] <= '0' + kTwistDepthMax && !td[1]) e->twist_depth = td[0] - '0';
+        if (td && td[0] >= '0' && td[0] <= '0' + kTwistDepthMax && !td[1]) e->opt.twist_depth = td[0] - '0';
     }
     {
         const char* ps = getenv("SECHS_PIPE_SERIAL");
-        e->pipe_serial = (ps && ps[0] == '1') ? 1 : 0;
+        e->opt.pipe_serial = (ps && ps[0] == '1') ? 1 : 0;
     }
-    e->pipe_dec = 1;  // decode-ahead where it applies: 0.0776 -> 0.069 ms per step same box
+    e->opt.pipe_dec = 1;  // decode-ahead where it applies: 0.0776 -> 0.069 ms per step same box
     {
         const char* pd = getenv("SECHS_PIPE_DEC");  // default override (A/B runs of whole legs)
-        if (pd && (pd[0] == '0' || pd[0] == '1')) e->pipe_dec = pd[0] - '0';
+        if (pd && (pd[0] == '0' || pd[0] == '1')) e->opt.pipe_dec = pd[0] - '0';
     }
-    e->pvalid = 0;
-    e->pcount = 0;
     if (rng_mode == SN_RNG_NUMPY_MT) {
         struct {
             void** p;
@@ -1762,18 +1787,18 @@ sn_status sn_create(sn_env** out, int device, int64_t num_games, int num_players
         // every record; SECHS_EV_SYSFENCE=1 restores it for A/B runs)
         const char* sf = getenv("SECHS_EV_SYSFENCE");
         const unsigned evf = hipEventDisableTiming | ((sf && sf[0] == '1') ? 0u : (unsigned)hipEventDisableSystemFence);
-        if (hipStreamCreateWithFlags(&e->side, hipStreamNonBlocking) != hipSuccess ||
-            hipStreamCreateWithFlags(&e->side2, hipStreamNonBlocking) != hipSuccess ||
-            hipEventCreateWithFlags(&e->ev_prep2, evf) != hipSuccess ||
-            hipEventCreateWithFlags(&e->ev_prep, evf) != hipSuccess ||
-            hipEventCreateWithFlags(&e->ev_main, evf) != hipSuccess ||
-            hipEventCreateWithFlags(&e->ev_play, evf) != hipSuccess) {
+        if (hipStreamCreateWithFlags(&e->pl.side, hipStreamNonBlocking) != hipSuccess ||
+            hipStreamCreateWithFlags(&e->pl.side2, hipStreamNonBlocking) != hipSuccess ||
+            hipEventCreateWithFlags(&e->pl.ev_prep2, evf) != hipSuccess ||
+            hipEventCreateWithFlags(&e->pl.ev_prep, evf) != hipSuccess ||
+            hipEventCreateWithFlags(&e->pl.ev_main, evf) != hipSuccess ||
+            hipEventCreateWithFlags(&e->pl.ev_play, evf) != hipSuccess) {
             sn_destroy(e);
             return fail(SN_EHIP, "stream/event creation failed");
         }
         for (int k = 0; k < 2; k++)
-            if (hipEventCreateWithFlags(&e->evt[k], evf) != hipSuccess ||
-                hipEventCreateWithFlags(&e->evd[k], evf) != hipSuccess) {
+            if (hipEventCreateWithFlags(&e->pl.evt[k], evf) != hipSuccess ||
+                hipEventCreateWithFlags(&e->pl.evd[k], evf) != hipSuccess) {
                 sn_destroy(e);
                 return fail(SN_EHIP, "stream/event creation failed");
             }
@@ -1809,18 +1834,18 @@ sn_status sn_destroy(sn_env* e) {
     (void)hipSetDevice(e->device);
     DevState& s = e->s;
     (void)hipDeviceSynchronize();  // no k_mt_ahead may still be in flight
-    if (e->ev_prep) (void)hipEventDestroy(e->ev_prep);
-    if (e->ev_main) (void)hipEventDestroy(e->ev_main);
-    if (e->ev_play) (void)hipEventDestroy(e->ev_play);
+    if (e->pl.ev_prep) (void)hipEventDestroy(e->pl.ev_prep);
+    if (e->pl.ev_main) (void)hipEventDestroy(e->pl.ev_main);
+    if (e->pl.ev_play) (void)hipEventDestroy(e->pl.ev_play);
     for (int k = 0; k < 2; k++) {
-        if (e->evt[k]) (void)hipEventDestroy(e->evt[k]);
-        if (e->evd[k]) (void)hipEventDestroy(e->evd[k]);
+        if (e->pl.evt[k]) (void)hipEventDestroy(e->pl.evt[k]);
+        if (e->pl.evd[k]) (void)hipEventDestroy(e->pl.evd[k]);
     }
-    if (e->ev_prep2) (void)hipEventDestroy(e->ev_prep2);
-    if (e->side2) (void)hipStreamDestroy(e->side2);
+    if (e->pl.ev_prep2) (void)hipEventDestroy(e->pl.ev_prep2);
+    if (e->pl.side2) (void)hipStreamDestroy(e->pl.side2);
     if (e->perr_host) (void)hipHostFree(e->perr_host);
     if (e->hbuf) (void)hipHostFree(e->hbuf);
-    if (e->side) (void)hipStreamDestroy(e->side);
+    if (e->pl.side) (void)hipStreamDestroy(e->pl.side);
     free_timing(e);
     void* ps[] = {s.hand, s.row_lo, s.row_hi, s.score, s.sum_res, s.episodes, s.mt_pos, s.ctr, s.mt, s.mt0, s.ring,
                   s.pring, s.pabsc, s.ptend, s.ptp, s.perr, s.lgs, s.lmem, s.drec};
@@ -1861,46 +1886,46 @@ sn_status sn_set_option(sn_env* e, int option, int value) {
         }
         case SN_OPT_CHUNK_STEPS:
             if (value < 1) return fail(SN_EINVAL, "chunk steps must be >= 1");
-            e->chunk_steps = value;
+            e->opt.chunk_steps = value;
             return SN_OK;
         case SN_OPT_PIPELINE:
             if (value != 0 && value != 1) return fail(SN_EINVAL, "pipeline must be 0 or 1");
-            e->pipe = value;
+            e->opt.pipe = value;
             return SN_OK;
         case SN_OPT_PIPE_GPW:
             if (value != 32 && value != 64) return fail(SN_EINVAL, "games per wave must be 32 or 64");
-            e->pipe_gpw = value;
+            e->opt.pipe_gpw = value;
             return SN_OK;
         case SN_OPT_PLAY_SPLIT:
             if (value < 0 || value > 1) return fail(SN_EINVAL, "play split must be 0 or 1");
-            e->play_split = value;
+            e->opt.play_split = value;
             return SN_OK;
         case SN_OPT_TWIST_EVERY:
             if (value < 1 || value > kTwistEveryMax) return fail(SN_EINVAL, "twist every must be 1 .. 5");
-            e->twist_every = value;
+            e->opt.twist_every = value;
             return SN_OK;
         case SN_OPT_TWIST_DEPTH:  // thresholds only: takes effect at the next twist, no pipeline restart
             if (value < 0 || value > kTwistDepthMax) return fail(SN_EINVAL, "twist depth must be 0 .. 3");
-            e->twist_depth = value;
+            e->opt.twist_depth = value;
             return SN_OK;
         case SN_OPT_TWIST_ROUND:
             if (value < 0 || value > 1) return fail(SN_EINVAL, "twist round must be 0 or 1");
-            e->twist_round = value;
+            e->opt.twist_round = value;
             return SN_OK;
         case SN_OPT_PLAY_QUAD:
         case SN_OPT_PIPE_FUSED:  // round-5 experiments, measured slower and removed
             return fail(SN_EUNSUPPORTED, "option removed (k_play_quad / the fused twist measured slower)");
         case SN_OPT_PIPE_DEC:
             if (value < 0 || value > 1) return fail(SN_EINVAL, "pipe dec must be 0 or 1");
-            e->pipe_dec = value;
+            e->opt.pipe_dec = value;
             return SN_OK;
         case SN_OPT_TWIST_SKIP:
             if (value < 0 || value > 1) return fail(SN_EINVAL, "twist skip must be 0 or 1");
-            e->twist_skip = value;
+            e->opt.twist_skip = value;
             return SN_OK;
         case SN_OPT_PIPE_LEAD:
             if (value < 64 || value > kPipeLead) return fail(SN_EINVAL, "pipe lead must be in 64..600");
-            e->pipe_lead = value;
+            e->opt.pipe_lead = value;
             return SN_OK;
         case SN_OPT_TIMING:
             if (value < 0 || value > 4096) return fail(SN_EINVAL, "timing launches must be in 0..4096");
@@ -1967,66 +1992,117 @@ sn_status sn_reset_to(sn_env* e, const int8_t* board, const int8_t* hands, void*
     return SN_OK;
 }
 
+// ---------------------------------------------------------------- the k_play launch plan
 // LDS per CU (gfx950); a k_play block (4 waves) must fit in it
 constexpr int kLdsBytes = 160 * 1024;
+
+// Observation rows of 48 bytes are staged: play_steps assembles a wave's rows
+// in LDS and stores them as 16-byte pieces (its `staged`), so such a launch
+// holds a staging area and sn_rollout / sn_league_rollout require the rows
+// 16-byte aligned (check_obs_align) -- before anything is launched.
+static constexpr bool obs_staged(const void* obs, int stride) { return obs && stride == 48; }
+
+static sn_status check_obs_align(const int8_t* obs, int stride) {
+    if (obs && (((uintptr_t)obs) & 3)) return fail(SN_EINVAL, "obs must be 4-byte aligned");
+    if (obs_staged(obs, stride) && (((uintptr_t)obs) & 15)) return fail(SN_EINVAL, "obs with stride 48 must be 16-byte aligned");
+    return SN_OK;
+}
+
+// The dynamic LDS of one k_play wave, by the kernel's RngMode: the lanes' deal decks or the obs staging
+// area (never live together, play_steps), then -- RNG_NUMPY_PIPE: the lanes' RingPipe windows (gpw = 32 or
+// 64 games per wave); RNG_NUMPY_RING: their copies of the k_mt_prep ring if the block still fits, else
+// ring_lds = 0 and RNG_NUMPY_RING_HBM plays; RNG_NUMPY_DEC: the staging area alone (no deck either);
+// every other mode: nothing more.  (k_play_split sizes its own: split_lds.)
+struct LdsPlan {
+    int wave;      // bytes per wave (PlayArgs::wave_lds)
+    int ring_lds;  // of them per lane for the ring copy / window, at the region's end (PlayArgs::ring_lds)
+};
+constexpr size_t block_lds(LdsPlan p) { return (size_t)p.wave * (kBlock / 64); }
+constexpr LdsPlan lds_plan(int N, bool staged, int mode, int gpw = 64, int ring_w = 0) {
+    const int stage = staged ? gpw * obs_stage_pieces(N) * 16 : 0, deal = gpw * kDealStride;
+    if (mode == RNG_NUMPY_DEC) return {stage ? stage : 16, 0};
+    const LdsPlan direct{deal > stage ? deal : stage, 0};
+    if (mode == RNG_NUMPY_PIPE) return {direct.wave + gpw * kPipeSlot, kPipeSlot};
+    const LdsPlan ring{direct.wave + 64 * ring_lds_stride(ring_w), ring_lds_stride(ring_w)};
+    return (mode == RNG_NUMPY_RING && block_lds(ring) <= (size_t)kLdsBytes) ? ring : direct;
+}
+// window: 240 + 30 bytes in whole 16-B chunks = 256, + 8 for the funnel's second read
+static_assert(kPipeSlot == 264, "RingPipe window per lane");
+// decks 64 x 212 = 13 568 (> staging 64 x 13 pieces x 16 = 13 312), windows 64 x 264 = 16 896
+static_assert(lds_plan(4, true, RNG_NUMPY_PIPE, 64).wave == 13568 + 16896 && lds_plan(4, true, RNG_NUMPY_PIPE).ring_lds == 264, "");
+// staging alone: 64 lanes x 13 pieces x 16 bytes
+static_assert(lds_plan(4, true, RNG_NUMPY_DEC).wave == 13312 && lds_plan(4, false, RNG_NUMPY_DEC).wave == 16, "");
+// staging 64 x 31 pieces x 16 = 31 744 (> decks 13 568)
+static_assert(lds_plan(10, true, RNG_PHILOX).wave == 31744 && lds_plan(10, false, RNG_NUMPY_MT).wave == 13568, "");
+// decks 13 568 + ring copies 64 x (256 + 8) = 16 896: 30 464 per wave, 121 856 per block <= 163 840
+static_assert(lds_plan(4, true, RNG_NUMPY_RING, 64, 256).wave == 30464 && lds_plan(4, true, RNG_NUMPY_RING, 64, 256).ring_lds == 264, "");
+// decks 13 568 + ring copies 64 x 520 = 33 280: 187 392 per block > 163 840, so the ring stays in HBM
+static_assert(lds_plan(4, true, RNG_NUMPY_RING, 64, 512).wave == 13568 && lds_plan(4, true, RNG_NUMPY_RING, 64, 512).ring_lds == 0, "");
+
+static void apply_plan(PlayArgs& a, LdsPlan p) { a.wave_lds = p.wave, a.ring_lds = p.ring_lds; }
+
+static PlayArgs rollout_args(int steps, int flags, int obs_stride, int32_t* rewards, uint8_t* done, uint8_t* actions, int8_t* obs) {
+    PlayArgs a{};
+    a.steps = steps, a.flags = flags, a.obs_stride = obs_stride;
+    a.rewards = rewards, a.done = done, a.actions_out = actions, a.obs = obs;
+    return a;
+}
+
+// env-steps [t0, t0 + n) of a rollout's arguments
+static PlayArgs slice_steps(const PlayArgs& a, int t0, int n, int64_t B, int64_t N) {
+    PlayArgs c = a;
+    c.steps = n;
+    c.step0 = a.step0 + t0;
+    if (a.rewards) c.rewards = a.rewards + (int64_t)t0 * B * N;
+    if (a.done) c.done = a.done + (int64_t)t0 * B;
+    if (a.actions_out) c.actions_out = a.actions_out + (int64_t)t0 * B * N;
+    if (a.obs) c.obs = a.obs + (int64_t)t0 * B * N * a.obs_stride;
+    return c;
+}
+
+
+// The k_play variants: (mode, games per wave, tournament handle) -> instantiation.  32 games per wave exist on
+// the pipelined ring only, league seats on it and on Philox.
+static sn_status launch_play_mode(const DevState& s, const PlayArgs& a, int mode, int gpw, hipStream_t st) {
+    const unsigned grid = (unsigned)((s.B + gpw * (kBlock / 64) - 1) / (gpw * (kBlock / 64)));
+    const size_t shmem = (size_t)a.wave_lds * (kBlock / 64);
+    const bool lg = s.lg_K != 0;
+    SN_DISPATCH_N(s.N, {
+        switch (mode) {
+            case RNG_NUMPY_MT: return (launch_k_play<NN, RNG_NUMPY_MT>(s, a, grid, shmem, st));
+            case RNG_NUMPY_RING: return (launch_k_play<NN, RNG_NUMPY_RING>(s, a, grid, shmem, st));
+            case RNG_NUMPY_RING_HBM: return (launch_k_play<NN, RNG_NUMPY_RING_HBM>(s, a, grid, shmem, st));
+            case RNG_NUMPY_DEC: return (launch_k_play<NN, RNG_NUMPY_DEC>(s, a, grid, shmem, st));
+            case RNG_NUMPY_PIPE:
+                if (gpw == 32) return (launch_k_play<NN, RNG_NUMPY_PIPE, 32>(s, a, grid, shmem, st));
+                return lg ? (launch_k_play<NN, RNG_NUMPY_PIPE, 64, true>(s, a, grid, shmem, st))
+                          : (launch_k_play<NN, RNG_NUMPY_PIPE>(s, a, grid, shmem, st));
+            default:
+                return lg ? (launch_k_play<NN, RNG_PHILOX, 64, true>(s, a, grid, shmem, st))
+                          : (launch_k_play<NN, RNG_PHILOX>(s, a, grid, shmem, st));
+        }
+    });
+    return SN_OK;
+}
 
 // k_play_split applies to in-kernel DrunkHamster rollouts of a handle whose
 // games are in lockstep (e->phase), with auto-reset, N <= kSplitMaxPlayers
 static bool split_ok(const sn_env* e, const PlayArgs& a) {
-    return e->play_split && e->phase >= 0 && (a.flags & SN_AUTO_RESET) && !a.actions && !a.invalid && !e->s.lg_K &&
-           e->s.N <= kSplitMaxPlayers && !(a.obs && a.obs_stride == 48 && (((uintptr_t)a.obs) & 15));
+    return e->opt.play_split && e->phase >= 0 && (a.flags & SN_AUTO_RESET) && !a.actions && !a.invalid && !e->s.lg_K &&
+           e->s.N <= kSplitMaxPlayers;
 }
 
+// one play launch outside the pipeline (ring-fed: behind its own k_mt_prep)
 static sn_status launch_play_one(sn_env* e, PlayArgs a, hipStream_t st) {
     const DevState& s = e->s;
-    const bool ring = (s.rng_mode == SN_RNG_NUMPY_MT) && !a.actions && s.ring_w > 0;
-    int wave = 64 * kDealStride;
-    if (a.obs && a.obs_stride == 48 && (((uintptr_t)a.obs) & 15) == 0) wave = max(wave, 64 * obs_stage_pieces(s.N) * 16);
-    a.ring_lds = 0;
-    const int ring_stride = ring_lds_stride(s.ring_w);
-    const bool ring_in_lds = ring && (wave + 64 * ring_stride) * (kBlock / 64) <= kLdsBytes;
-    if (ring_in_lds) {
-        a.ring_lds = ring_stride;
-        wave += 64 * ring_stride;
-    }
-    a.wave_lds = wave;
-    a.vec_out = ((((uintptr_t)a.rewards) & 15) == 0) && ((((uintptr_t)a.actions_out) & 3) == 0);
-    const size_t shmem = (size_t)wave * (kBlock / 64);
-    if (a.obs && a.obs_stride == 48 && (((uintptr_t)a.obs) & 15)) return fail(SN_EINVAL, "obs with stride 48 must be 16-byte aligned");
-    if (ring) {
-        constexpr int GPW = kPrepGamesPerWave;
-        const dim3 pg((unsigned)((s.B + GPW * (kBlock / 64) - 1) / (GPW * (kBlock / 64))));
-        switch (s.ring_w / 64) {
-            case 1: hipLaunchKernelGGL((k_mt_prep<1, GPW>), pg, dim3(kBlock), 0, st, s); break;
-            case 2: hipLaunchKernelGGL((k_mt_prep<2, GPW>), pg, dim3(kBlock), 0, st, s); break;
-            case 3: hipLaunchKernelGGL((k_mt_prep<3, GPW>), pg, dim3(kBlock), 0, st, s); break;
-            case 4: hipLaunchKernelGGL((k_mt_prep<4, GPW>), pg, dim3(kBlock), 0, st, s); break;
-            case 5: hipLaunchKernelGGL((k_mt_prep<5, GPW>), pg, dim3(kBlock), 0, st, s); break;
-            case 6: hipLaunchKernelGGL((k_mt_prep<6, GPW>), pg, dim3(kBlock), 0, st, s); break;
-            case 7: hipLaunchKernelGGL((k_mt_prep<7, GPW>), pg, dim3(kBlock), 0, st, s); break;
-            case 8: hipLaunchKernelGGL((k_mt_prep<8, GPW>), pg, dim3(kBlock), 0, st, s); break;
-            default: return fail(SN_EINVAL, "bad ring size");
-        }
-        if (ring_in_lds) {
-            SN_DISPATCH_N(s.N, {
-                HIP_TRY(hipFuncSetAttribute((const void*)k_play<NN, RNG_NUMPY_RING>,
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
-                hipLaunchKernelGGL((k_play<NN, RNG_NUMPY_RING>), dim3(grid_for(s.B)), dim3(kBlock), shmem, st, s, a);
-            });
-        } else {
-            SN_DISPATCH_N(s.N, {
-                HIP_TRY(hipFuncSetAttribute((const void*)k_play<NN, RNG_NUMPY_RING_HBM>,
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
-                hipLaunchKernelGGL((k_play<NN, RNG_NUMPY_RING_HBM>), dim3(grid_for(s.B)), dim3(kBlock), shmem, st, s, a);
-            });
-        }
-    } else if (s.rng_mode == SN_RNG_NUMPY_MT) {
-        SN_DISPATCH_N(s.N, {
-            HIP_TRY(hipFuncSetAttribute((const void*)k_play<NN, RNG_NUMPY_MT>,
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
-            hipLaunchKernelGGL((k_play<NN, RNG_NUMPY_MT>), dim3(grid_for(s.B)), dim3(kBlock), shmem, st, s, a);
-        });
-    } else if (split_ok(e, a) && a.steps <= kHand) {  // at most one deal per launch
+    int mode = RNG_PHILOX;
+    if (s.rng_mode == SN_RNG_NUMPY_MT) mode = (!a.actions && s.ring_w > 0) ? RNG_NUMPY_RING : RNG_NUMPY_MT;
+    const LdsPlan plan = lds_plan(s.N, obs_staged(a.obs, a.obs_stride), mode, 64, s.ring_w);
+    apply_plan(a, plan);
+    if (mode == RNG_NUMPY_RING) {
+        if (const sn_status r = launch_mt_prep(s, st); r != SN_OK) return r;
+        if (!plan.ring_lds) mode = RNG_NUMPY_RING_HBM;
+    } else if (mode == RNG_PHILOX && split_ok(e, a) && a.steps <= kHand) {  // at most one deal per launch
         a.n0 = kHand - e->phase;
         SN_DISPATCH_N(s.N, {
             if constexpr (NN <= kSplitMaxPlayers) {
@@ -2036,30 +2112,27 @@ static sn_status launch_play_one(sn_env* e, PlayArgs a, hipStream_t st) {
                 hipLaunchKernelGGL((k_play_split<NN, RNG_PHILOX>), dim3(grid_for(s.B)), dim3(2 * kBlock), sl, st, s, a);
             }
         });
-    } else {
-        SN_DISPATCH_N(s.N, {
-            if (s.lg_K) {
-                if constexpr (NN >= 2 && NN <= kLeagueMaxPlayers) {
-                    HIP_TRY(hipFuncSetAttribute((const void*)k_play<NN, RNG_PHILOX, 64, true>,
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
-                    hipLaunchKernelGGL((k_play<NN, RNG_PHILOX, 64, true>), dim3(grid_for(s.B)), dim3(kBlock), shmem, st, s, a);
-                }
-            } else {
-                HIP_TRY(hipFuncSetAttribute((const void*)k_play<NN, RNG_PHILOX>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                            (int)shmem));
-                hipLaunchKernelGGL((k_play<NN, RNG_PHILOX>), dim3(grid_for(s.B)), dim3(kBlock), shmem, st, s, a);
-            }
-        });
+        HIP_TRY(hipGetLastError());
+        return SN_OK;
     }
-    HIP_TRY(hipGetLastError());
-    return SN_OK;
+    return launch_play_mode(s, a, mode, 64, st);
 }
 
-// A ring-fed (numpy-MT, in-kernel DrunkHamster) rollout runs in launches of
-// at most chunk_steps env-steps, each behind its own k_mt_prep, so that one
-// ring covers a launch's draws (a 4-player episode: 193.5 +- 9.3 words).
+// Slots by index: play launch p reads the consumer position launch p-1 left
+// in pabsc and writes its own; twist G writes its twisted end to ptend, read
+// by the launches of group G+1; decode G leaves the decoder's position in the
+// two pabsc slots past the play launches'.  The start-up twist and decode
+// count as index -1 (kStartUp), its consumer position as launch -1's.
+constexpr uint64_t kStartUp = ~0ull;
+constexpr uint32_t kSlotMask = (uint32_t)kPipeSlots - 1u;
+static inline int pabsc_in(uint64_t p) { return (int)((p + kSlotMask) & kSlotMask); }
+static inline int pabsc_out(uint64_t p) { return (int)(p & kSlotMask); }
+static inline int ptend_slot(uint64_t G) { return (int)(G & 1u); }
+static inline int dec_slot(uint64_t G) { return kDecSlot + (int)(G & 1u); }
+static inline int dec_record(int64_t episode) { return (int)(episode % kDecRecords); }  // drec slot of an episode's record
+
 sn_status sn_pipe_sync(sn_env* e, hipStream_t st) {
-    if (!e || !e->pvalid) return SN_OK;
+    if (!e || !e->pl.valid) return SN_OK;
     // k_pipe_code reads the last k_play's consumer position (pabsc) and the
     // last k_mt_ahead's twisted end: wait for both, whatever stream `st` is
     // (the null stream does not order behind a non-blocking caller stream).
@@ -2067,16 +2140,16 @@ sn_status sn_pipe_sync(sn_env* e, hipStream_t st) {
     // was enqueued (launch_pipe), on the caller's stream of that call -- so no
     // stream of an earlier call is touched here; ev_prep is recorded now,
     // behind everything enqueued so far on the side stream.
-    HIP_TRY(hipStreamWaitEvent(st, e->ev_play, 0));
-    HIP_TRY(hipEventRecord(e->ev_prep, e->side));
-    HIP_TRY(hipStreamWaitEvent(st, e->ev_prep, 0));
-    HIP_TRY(hipEventRecord(e->ev_prep2, e->side2));  // the decodes (their ring reads) are done too
-    HIP_TRY(hipStreamWaitEvent(st, e->ev_prep2, 0));
+    HIP_TRY(hipStreamWaitEvent(st, e->pl.ev_play, 0));
+    HIP_TRY(hipEventRecord(e->pl.ev_prep, e->pl.side));
+    HIP_TRY(hipStreamWaitEvent(st, e->pl.ev_prep, 0));
+    HIP_TRY(hipEventRecord(e->pl.ev_prep2, e->pl.side2));  // the decodes (their ring reads) are done too
+    HIP_TRY(hipStreamWaitEvent(st, e->pl.ev_prep2, 0));
     // the last play launch wrote pabsc[pl_cout]; the last twist ptend[tw_out]
     hipLaunchKernelGGL(k_pipe_code, dim3((unsigned)((e->s.B + kBlock / 64 - 1) / (kBlock / 64))), dim3(kBlock), 0, st,
-                       e->s, e->pl_cout, e->tw_out);
+                       e->s, e->pl.pl_cout, e->pl.tw_out);
     HIP_TRY(hipGetLastError());
-    e->pvalid = 0;
+    e->pl.valid = 0;
     return SN_OK;
 }
 
@@ -2091,53 +2164,12 @@ sn_status sn_pipe_sync(sn_env* e, hipStream_t st) {
 // launches (one episode per pair) it is <= 6.1e-73 for every N <= 10.
 static int pipe_max_chunk(int N) { return N <= 4 ? 10 : 5; }
 
-// LDS a pipelined k_play block needs (obs staging / deck + the RingPipe windows)
-static size_t pipe_lds(const DevState& s, const PlayArgs& a, int gpw, int* wave_out) {
-    int wave = gpw * kDealStride;
-    if (a.obs && a.obs_stride == 48 && (((uintptr_t)a.obs) & 15) == 0) wave = max(wave, gpw * obs_stage_pieces(s.N) * 16);
-    wave += gpw * kPipeSlot;
-    *wave_out = wave;
-    return (size_t)wave * (kBlock / 64);
-}
-
-// one pipelined play launch
-static sn_status pipe_play(const DevState& s, const PlayArgs& c, int gpw, unsigned nblk, size_t shmem, hipStream_t st) {
-    SN_DISPATCH_N(s.N, {
-        if (gpw == 32) {
-            HIP_TRY(hipFuncSetAttribute((const void*)k_play<NN, RNG_NUMPY_PIPE, 32>,
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
-            hipLaunchKernelGGL((k_play<NN, RNG_NUMPY_PIPE, 32>), dim3(nblk), dim3(kBlock), shmem, st, s, c);
-        } else if (s.lg_K) {
-            if constexpr (NN >= 2 && NN <= kLeagueMaxPlayers) {
-                HIP_TRY(hipFuncSetAttribute((const void*)k_play<NN, RNG_NUMPY_PIPE, 64, true>,
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
-                hipLaunchKernelGGL((k_play<NN, RNG_NUMPY_PIPE, 64, true>), dim3(nblk), dim3(kBlock), shmem, st, s, c);
-            }
-        } else {
-            HIP_TRY(hipFuncSetAttribute((const void*)k_play<NN, RNG_NUMPY_PIPE>,
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
-            hipLaunchKernelGGL((k_play<NN, RNG_NUMPY_PIPE>), dim3(nblk), dim3(kBlock), shmem, st, s, c);
-        }
-    });
-    HIP_TRY(hipGetLastError());
-    return SN_OK;
-}
-
-// The pipelined numpy-MT rollout: per launch of <= 10 env-steps, k_play (on
-// the caller's stream) draws from words k_mt_ahead twisted during the
-// previous launch, while the next k_mt_ahead runs on the side stream.
-// Hand-off: HIP events both ways -- a wait and a record on the caller's
-// stream between play launches.  (Device-flag and in-launch hand-offs were
-// built and measured slower on gfx950; DESIGN.md §4.)
-// one decode-ahead play launch (RNG_NUMPY_DEC: N <= 4, 64 games per wave)
-static sn_status dec_play(const DevState& s, const PlayArgs& c, size_t shmem, hipStream_t st) {
-    SN_DISPATCH_N(s.N, {
-        if constexpr (NN <= kSplitMaxPlayers) {
-            HIP_TRY(hipFuncSetAttribute((const void*)k_play<NN, RNG_NUMPY_DEC>,
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
-            hipLaunchKernelGGL((k_play<NN, RNG_NUMPY_DEC>), dim3(grid_for(s.B)), dim3(kBlock), shmem, st, s, c);
-        }
-    });
+static sn_status launch_ahead(const DevState& s, bool init, bool round_tw, const AheadArgs& aa, hipStream_t st) {
+    const dim3 pg((unsigned)((s.B + kBlock / 64 - 1) / (kBlock / 64)));
+    if (init && round_tw) hipLaunchKernelGGL((k_mt_ahead<true, true>), pg, dim3(kBlock), 0, st, s, aa);
+    else if (init) hipLaunchKernelGGL((k_mt_ahead<true, false>), pg, dim3(kBlock), 0, st, s, aa);
+    else if (round_tw) hipLaunchKernelGGL((k_mt_ahead<false, true>), pg, dim3(kBlock), 0, st, s, aa);
+    else hipLaunchKernelGGL((k_mt_ahead<false, false>), pg, dim3(kBlock), 0, st, s, aa);
     HIP_TRY(hipGetLastError());
     return SN_OK;
 }
@@ -2145,7 +2177,7 @@ static sn_status dec_play(const DevState& s, const PlayArgs& c, size_t shmem, hi
 // records of episodes [e0, e0 + ne) (global counter since the pipeline start) on stream st
 static sn_status dec_launch(sn_env* e, int64_t e0, int ne, int phi0, int tpar, int cin, int cout, hipStream_t st) {
     const DevState& s = e->s;
-    const DecArgs d{(int)(e0 % kDecRecords), ne, phi0, tpar, cin, cout};
+    const DecArgs d{dec_record(e0), ne, phi0, tpar, cin, cout};
     const dim3 grid((unsigned)((s.B + kDecBlock - 1) / kDecBlock));
     SN_DISPATCH_N(s.N, {
         if constexpr (NN <= kSplitMaxPlayers) hipLaunchKernelGGL((k_decode<NN>), grid, dim3(kDecBlock), 0, st, s, d);
@@ -2159,207 +2191,191 @@ static sn_status dec_launch(sn_env* e, int64_t e0, int ne, int phi0, int tpar, i
 // (e->phase known): every launch's random decisions are then the same
 // function of the stream for every game.
 static bool dec_ok(const sn_env* e, const PlayArgs& a) {
-    return e->pipe_dec && e->phase >= 0 && (a.flags & SN_AUTO_RESET) && !a.actions && !a.invalid && !e->s.lg_K &&
-           e->s.N <= kSplitMaxPlayers && e->pipe_gpw == 64 && e->s.drec;
+    return e->opt.pipe_dec && e->phase >= 0 && (a.flags & SN_AUTO_RESET) && !a.actions && !a.invalid && !e->s.lg_K &&
+           e->s.N <= kSplitMaxPlayers && e->opt.pipe_gpw == 64 && e->s.drec;
 }
 
-static sn_status launch_pipe(sn_env* e, PlayArgs a, hipStream_t st) {
-    DevState& s = e->s;
-    int wave;
-    const int gpw = e->pipe_gpw;
-    const bool dec = dec_ok(e, a);
-    size_t shmem = pipe_lds(s, a, gpw, &wave);
-    a.ring_lds = kPipeSlot;
-    if (dec) {  // the obs staging only (no deck, no ring window)
-        wave = (a.obs && a.obs_stride == 48 && (((uintptr_t)a.obs) & 15) == 0) ? 64 * obs_stage_pieces(s.N) * 16 : 16;
-        shmem = (size_t)wave * (kBlock / 64);
-        a.ring_lds = 0;
-    }
-    a.wave_lds = wave;
-    a.vec_out = ((((uintptr_t)a.rewards) & 15) == 0) && ((((uintptr_t)a.actions_out) & 3) == 0);
-    const dim3 pg((unsigned)((s.B + kBlock / 64 - 1) / (kBlock / 64)));
-    const int64_t B = s.B, N = s.N;
-    // SN_OPT_TWIST_EVERY = K: play launches in groups of K; beside the first
-    // launch p of group G runs twist G, leading the consumer position of
-    // launch p-1 by 600 K words -- the 2K launches p .. p+2K-1, i.e. K
-    // launch pairs of the §4 tail bound -- and launch p waits for twist G-1
-    // only, which had a whole group of launches to finish.  Per group, one
-    // record and one wait on the caller's stream (K = 1: the launch before).
-    // Slots: pabsc by launch index mod kPipeSlots (8 >= K + 3: the next writer
-    // of launch p-1's slot is launch p+7, in group G+1 or later, which is
-    // ordered behind twist G -- the reader of that slot), ptend by group
-    // parity (INIT = launch -1 / twist -1).  The ring holds the lead, the
-    // SN_OPT_TWIST_DEPTH rounds a refill adds and a round's overshoot for K <= 5
-    // (kPipeSpanMax, sechs_state.h), and mt0 the word-0 crossings of that span.
-    const int K = e->twist_every;
-    const bool round_tw = e->twist_round;
-    if (e->pvalid && (e->pK != K || (e->pdec != 0) != dec)) {  // restart with the other group size / form
-        const sn_status r = sn_pipe_sync(e, st);
+// Start the pipeline from mt_pos: twist the lead ahead, synchronously (on the caller's stream).
+static sn_status pipe_start(sn_env* e, int K, bool dec, int lead, hipStream_t st) {
+    sn_env::Pipeline& pl = e->pl;
+    // decode-ahead: the start position to the decoder's input slot of the first decode and
+    // the play slot (a sync before any play launch exports it)
+    const AheadArgs aa{dec ? dec_slot(kStartUp - 1) : pabsc_out(kStartUp), ptend_slot(kStartUp - 1), ptend_slot(kStartUp), lead,
+                       e->perr_host_dev, dec ? pabsc_out(kStartUp) : -1, e->opt.twist_depth};
+    pl.tw_out = ptend_slot(kStartUp), pl.pl_cout = pabsc_out(kStartUp), pl.launches = 0;
+    if (const sn_status r = launch_ahead(e->s, true, e->opt.twist_round, aa, st); r != SN_OK) return r;
+    if (dec) {  // the records of the first group's launches (episodes 0 .. K), from the current step on
+        pl.dec_e = 0;
+        const sn_status r = dec_launch(e, 0, K + 1, e->phase, ptend_slot(kStartUp), dec_slot(kStartUp - 1), dec_slot(kStartUp), st);
         if (r != SN_OK) return r;
+        pl.dec_next = K + 1;
     }
-    // Decode-ahead: twist G runs on `side` CONCURRENTLY with decode G on `side2`, so it leads
-    // the decoder position after decode G-1 (slot kDecSlot + ((G - 1) & 1)) by the words of
-    // the 2K + 1 episodes decode G+1 may need: 600 (K + 1) words (~200 per episode at N <= 4;
-    // the ring holds the lead + the refill depth + a round, kPipeSpanMax), and the play launches read no ring at
-    // all.  Otherwise the twists lead the play consumer by 600 K words.
-    const int lead = dec ? min(e->pipe_lead * (K + 1), kPipeRing - kMtN) : e->pipe_lead * K;
-    static_assert(kPipeLeadMax <= kPipeRing - kMtN, "the decode-ahead lead is never capped by the ring");
-    constexpr uint32_t kSlotMask = (uint32_t)kPipeSlots - 1u;
-    if (!e->pvalid) {  // start the pipeline from mt_pos: twist the lead ahead, synchronously
-        // decode-ahead: the start position to the decoder's input slot of the first decode and
-        // the play slot (a sync before any play launch exports it)
-        const AheadArgs aa{dec ? kDecSlot : (int)kSlotMask, 0, 1, lead, e->perr_host_dev, dec ? (int)kSlotMask : -1, e->twist_depth};
-        e->tw_out = 1, e->pl_cout = (int)kSlotMask, e->pphase = 0;
-        if (round_tw) hipLaunchKernelGGL((k_mt_ahead<true, true>), pg, dim3(kBlock), 0, st, s, aa);
-        else hipLaunchKernelGGL((k_mt_ahead<true, false>), pg, dim3(kBlock), 0, st, s, aa);
-        HIP_TRY(hipGetLastError());
-        if (dec) {  // the records of the first group's launches (episodes 0 .. K), from the current step on
-            e->dec_e = 0;
-            const sn_status r = dec_launch(e, 0, K + 1, e->phase, 1, kDecSlot, kDecSlot + 1, st);  // "decode -1"
-            if (r != SN_OK) return r;
-            e->dec_next = K + 1;
+    HIP_TRY(hipEventRecord(pl.ev_prep, st));
+    pl.valid = 1, pl.K = K, pl.dec = dec ? 1 : 0;
+    return SN_OK;
+}
+
+// Twist G on `side` -- and, decode-ahead, decode G on `side2` -- beside play launch p, the first of group G, which
+// started in episode e_start.  ti: the launch's SN_OPT_TIMING events (-1: none).
+static sn_status pipe_twist(sn_env* e, uint64_t G, uint64_t p, int64_t e_start, int lead, int ti, hipStream_t st) {
+    sn_env::Pipeline& pl = e->pl;
+    hipEvent_t* tv = (ti >= 0) ? e->tev + kTimingEvents * ti : nullptr;
+    // beside this launch (SECHS_PIPE_SERIAL=1, diagnostics: after it -- solo kernel times)
+    if (e->opt.pipe_serial) HIP_TRY(hipEventRecord(pl.ev_main, st));
+    HIP_TRY(hipStreamWaitEvent(pl.side, pl.ev_main, 0));
+    if (tv) HIP_TRY(hipEventRecord(tv[2], pl.side));
+    // SN_OPT_TWIST_SKIP (tests only): the overrun detector under the default schedule
+    const AheadArgs aa{pl.dec ? dec_slot(G - 1) : pabsc_in(p), ptend_slot(G - 1), ptend_slot(G),
+                       (e->opt.twist_skip && G >= 1u) ? 0 : lead, e->perr_host_dev, -1, e->opt.twist_depth};
+    if (const sn_status r = launch_ahead(e->s, false, e->opt.twist_round, aa, pl.side); r != SN_OK) return r;
+    if (tv) HIP_TRY(hipEventRecord(tv[3], pl.side));
+    if (pl.dec) {
+        // decode G on side2, concurrent with twist G: the records group G+1 may touch --
+        // its launches start at most K episodes past this launch's and touch at most one
+        // more each: episodes < e_start + 2K + 1 (the ring of kDecRecords >= 2K + 2
+        // slots never overwrites one a running launch reads: the oldest, launch p-K,
+        // reads episodes >= e_start - K, 3K + 1 <= kDecRecords).  It reads the words twist
+        // G-1 twisted and waits for that twist only (which waited for launch p-K-1), and
+        // its position goes to the decoder slot of decode G, which twist G+1 reads.
+        const int64_t target = e_start + 2 * pl.K + 1;
+        // (group 0: the start-up twist and decode ran on the play stream, before ev_main)
+        if (e->opt.pipe_serial || G == 0u) HIP_TRY(hipStreamWaitEvent(pl.side2, pl.ev_main, 0));
+        if (G >= 1u) HIP_TRY(hipStreamWaitEvent(pl.side2, pl.evt[ptend_slot(G - 1)], 0));
+        if (tv) HIP_TRY(hipEventRecord(tv[4], pl.side2));
+        const int ne = target > pl.dec_next ? (int)(target - pl.dec_next) : 0;
+        // ne == 0 (short launches): still a launch, so the position moves to decode G's slot
+        const sn_status r = dec_launch(e, pl.dec_next, ne, 0, ptend_slot(G - 1), dec_slot(G - 1), dec_slot(G), pl.side2);
+        if (r != SN_OK) return r;
+        pl.dec_next = max(pl.dec_next, target);
+        if (tv) {
+            HIP_TRY(hipEventRecord(tv[5], pl.side2));
+            e->tev_tw[ti] |= 2;
         }
-        HIP_TRY(hipEventRecord(e->ev_prep, st));
-        e->pvalid = 1;
-        e->pK = K;
-        e->pdec = dec ? 1 : 0;
+        HIP_TRY(hipEventRecord(pl.evd[ptend_slot(G)], pl.side2));
+    }
+    HIP_TRY(hipEventRecord(pl.evt[ptend_slot(G)], pl.side));
+    HIP_TRY(hipEventRecord(pl.ev_prep, pl.side));
+    pl.tw_out = ptend_slot(G);
+    return SN_OK;
+}
+
+// The pipelined numpy-MT rollout: per launch of <= 10 env-steps, k_play (on
+// the caller's stream) draws from words k_mt_ahead twisted during the
+// previous launch, while the next k_mt_ahead runs on the side stream.
+// Hand-off: HIP events both ways -- a wait and a record on the caller's
+// stream between play launches.  (Device-flag and in-launch hand-offs were
+// built and measured slower on gfx950; DESIGN.md §4.)
+//
+// SN_OPT_TWIST_EVERY = K: play launches in groups of K; beside the first
+// launch p of group G runs twist G, leading the consumer position of
+// launch p-1 by 600 K words -- the 2K launches p .. p+2K-1, i.e. K
+// launch pairs of the §4 tail bound -- and launch p waits for twist G-1
+// only, which had a whole group of launches to finish.  Per group, one
+// record and one wait on the caller's stream (K = 1: the launch before).
+// Slots: pabsc by launch index mod kPipeSlots (8 >= K + 3: the next writer
+// of launch p-1's slot is launch p+7, in group G+1 or later, which is
+// ordered behind twist G -- the reader of that slot), ptend by group
+// parity.  The ring holds the lead, the SN_OPT_TWIST_DEPTH rounds a refill
+// adds and a round's overshoot for K <= 5 (kPipeSpanMax, sechs_state.h), and
+// mt0 the word-0 crossings of that span.
+//
+// Decode-ahead: twist G runs on `side` CONCURRENTLY with decode G on `side2`,
+// so it leads the decoder position after decode G-1 by the words of the
+// 2K + 1 episodes decode G+1 may need: 600 (K + 1) words (~200 per episode at
+// N <= 4), and the play launches (one launch plan: no deck, no ring window)
+// read no ring at all.  Otherwise the twists lead the play consumer by 600 K words.
+static sn_status launch_pipe(sn_env* e, PlayArgs a, LdsPlan plan, hipStream_t st) {
+    const DevState& s = e->s;
+    sn_env::Pipeline& pl = e->pl;
+    const int gpw = e->opt.pipe_gpw, K = e->opt.twist_every;
+    const bool dec = dec_ok(e, a);
+    const int mode = dec ? RNG_NUMPY_DEC : RNG_NUMPY_PIPE;
+    apply_plan(a, dec ? lds_plan(s.N, obs_staged(a.obs, a.obs_stride), RNG_NUMPY_DEC) : plan);
+    if (pl.valid && (pl.K != K || (pl.dec != 0) != dec)) {  // restart with the other group size / form
+        if (const sn_status r = sn_pipe_sync(e, st); r != SN_OK) return r;
+    }
+    const int lead = dec ? min(e->opt.pipe_lead * (K + 1), kPipeRing - kMtN) : e->opt.pipe_lead * K;
+    static_assert(kPipeLeadMax <= kPipeRing - kMtN, "the decode-ahead lead is never capped by the ring");
+    if (!pl.valid) {
+        if (const sn_status r = pipe_start(e, K, dec, lead, st); r != SN_OK) return r;
     } else {
         // order behind the last pipelined k_play (recorded on the stream of
         // that call): always, also on the same stream -- a stream handle's
         // value may be reused by a new stream once the caller destroyed the
         // old one, and a wait on an event already behind costs ~nothing
-        HIP_TRY(hipStreamWaitEvent(st, e->ev_play, 0));
+        HIP_TRY(hipStreamWaitEvent(st, pl.ev_play, 0));
     }
     // a tournament game adds its seat draw (<= K - 1 + 1 draws): 10-step
     // launches keep the pair tail < 1e-26 up to K = 8 agents at N <= 4
     // (tools/pipe_tail.py), beyond that 5-step launches
-    const int chunk = min(e->chunk_steps, (s.lg_K > 8) ? 5 : pipe_max_chunk(s.N));
+    const int chunk = min(e->opt.chunk_steps, (s.lg_K > 8) ? 5 : pipe_max_chunk(s.N));
     int phase = dec ? e->phase : 0;  // decode-ahead: the games' step within their episode
-    const unsigned nblk = (gpw == 32) ? (unsigned)((s.B + 32 * (kBlock / 64) - 1) / (32 * (kBlock / 64)))
-                                      : (unsigned)grid_for(s.B);
     for (int t0 = 0; t0 < a.steps; t0 += chunk) {
-        PlayArgs c = a;
-        c.steps = min(chunk, a.steps - t0);
-        c.step0 = a.step0 + t0;
-        if (a.rewards) c.rewards = a.rewards + (int64_t)t0 * B * N;
-        if (a.done) c.done = a.done + (int64_t)t0 * B;
-        if (a.actions_out) c.actions_out = a.actions_out + (int64_t)t0 * B * N;
-        if (a.obs) c.obs = a.obs + (int64_t)t0 * B * N * a.obs_stride;
-        const uint64_t p = e->pphase;
-        c.pipe_cin = (int)((p + kSlotMask) & kSlotMask), c.pipe_cout = (int)(p & kSlotMask);
+        PlayArgs c = slice_steps(a, t0, min(chunk, a.steps - t0), s.B, s.N);
+        const uint64_t p = pl.launches, G = p / (uint64_t)K;
+        const bool first = (p % (uint64_t)K) == 0u;  // twist G beside this launch
+        c.pipe_cin = pabsc_in(p), c.pipe_cout = pabsc_out(p);
+        c.pipe_t = ptend_slot(G - 1);  // twist G-1's end (the start-up's for group 0)
         if (dec) {  // the launch's records: its episode's and (crossing a deal) the next one's
             c.n0 = phase;
-            c.drec0 = (int)(e->dec_e % kDecRecords), c.drec1 = (int)((e->dec_e + 1) % kDecRecords);
+            c.drec0 = dec_record(pl.dec_e), c.drec1 = dec_record(pl.dec_e + 1);
         }
-        const uint64_t G = p / (uint64_t)K;
-        const bool first = (p % (uint64_t)K) == 0u;  // twist G beside this launch
-        c.pipe_t = (int)((G + 1u) & 1u);              // twist G-1's end (INIT's for group 0)
         // twist G-1 (decode-ahead: decode G-1, which waited for twist G-1 itself)
-        if (first && G >= 1u) HIP_TRY(hipStreamWaitEvent(st, (dec ? e->evd : e->evt)[(G + 1u) & 1u], 0));
-        if (first && !e->pipe_serial) HIP_TRY(hipEventRecord(e->ev_main, st));  // launch p-1's consumption is final
+        if (first && G >= 1u) HIP_TRY(hipStreamWaitEvent(st, (dec ? pl.evd : pl.evt)[ptend_slot(G - 1)], 0));
+        if (first && !e->opt.pipe_serial) HIP_TRY(hipEventRecord(pl.ev_main, st));  // launch p-1's consumption is final
         const int ti = (e->tn < e->tcap) ? e->tn++ : -1;  // SN_OPT_TIMING: this launch's events
         hipEvent_t* tv = (ti >= 0) ? e->tev + kTimingEvents * ti : nullptr;
         if (tv) e->tev_tw[ti] = first ? 1 : 0;
         if (tv) HIP_TRY(hipEventRecord(tv[0], st));
-        {
-            const sn_status r = dec ? dec_play(s, c, shmem, st) : pipe_play(s, c, gpw, nblk, shmem, st);
-            if (r != SN_OK) return r;
-        }
-        const int64_t e_start = e->dec_e;  // the episode this launch started in
+        if (const sn_status r = launch_play_mode(s, c, mode, gpw, st); r != SN_OK) return r;  // decode-ahead: gpw == 64
+        const int64_t e_start = pl.dec_e;  // the episode this launch started in
         if (dec) {
             phase += c.steps;
-            if (phase >= kHand) phase -= kHand, e->dec_e++;
+            if (phase >= kHand) phase -= kHand, pl.dec_e++;
         }
         if (tv) HIP_TRY(hipEventRecord(tv[1], st));
         if (first) {
-            // twist G, beside this launch (SECHS_PIPE_SERIAL=1, diagnostics: after it -- solo kernel times)
-            if (e->pipe_serial) HIP_TRY(hipEventRecord(e->ev_main, st));
-            HIP_TRY(hipStreamWaitEvent(e->side, e->ev_main, 0));
-            if (tv) HIP_TRY(hipEventRecord(tv[2], e->side));
-            // SN_OPT_TWIST_SKIP (tests only): the overrun detector under the default schedule
-            const AheadArgs aa{dec ? kDecSlot + (int)((G + 1u) & 1u) : c.pipe_cin, c.pipe_t, (int)(G & 1u),
-                               (e->twist_skip && G >= 1u) ? 0 : lead, e->perr_host_dev, -1, e->twist_depth};
-            if (round_tw) hipLaunchKernelGGL((k_mt_ahead<false, true>), pg, dim3(kBlock), 0, e->side, s, aa);
-            else hipLaunchKernelGGL((k_mt_ahead<false, false>), pg, dim3(kBlock), 0, e->side, s, aa);
-            HIP_TRY(hipGetLastError());
-            if (tv) HIP_TRY(hipEventRecord(tv[3], e->side));
-            if (dec) {
-                // decode G on side2, concurrent with twist G: the records group G+1 may touch --
-                // its launches start at most K episodes past this launch's and touch at most one
-                // more each: episodes < e_start + 2K + 1 (the ring of kDecRecords >= 2K + 2
-                // slots never overwrites one a running launch reads: the oldest, launch p-K,
-                // reads episodes >= e_start - K, 3K + 1 <= kDecRecords).  It reads the words twist
-                // G-1 twisted (ptend slot (G-1) & 1) and waits for that twist only (which waited
-                // for launch p-K-1), and its position goes to slot kDecSlot + (G & 1), which
-                // twist G+1 reads.
-                const int64_t target = e_start + 2 * K + 1;
-                // (group 0: the start-up twist and decode ran on the play stream, before ev_main)
-                if (e->pipe_serial || G == 0u) HIP_TRY(hipStreamWaitEvent(e->side2, e->ev_main, 0));
-                if (G >= 1u) HIP_TRY(hipStreamWaitEvent(e->side2, e->evt[(G + 1u) & 1u], 0));
-                if (tv) HIP_TRY(hipEventRecord(tv[4], e->side2));
-                const int ne = target > e->dec_next ? (int)(target - e->dec_next) : 0;
-                // ne == 0 (short launches): still a launch, so the position moves to slot G & 1
-                const sn_status r = dec_launch(e, e->dec_next, ne, 0, (int)((G + 1u) & 1u),
-                                               kDecSlot + (int)((G + 1u) & 1u), kDecSlot + (int)(G & 1u), e->side2);
-                if (r != SN_OK) return r;
-                e->dec_next = max(e->dec_next, target);
-                if (tv) {
-                    HIP_TRY(hipEventRecord(tv[5], e->side2));
-                    e->tev_tw[ti] |= 2;
-                }
-                HIP_TRY(hipEventRecord(e->evd[G & 1u], e->side2));
-            }
-            HIP_TRY(hipEventRecord(e->evt[G & 1u], e->side));
-            HIP_TRY(hipEventRecord(e->ev_prep, e->side));
-            e->tw_out = (int)(G & 1u);
+            if (const sn_status r = pipe_twist(e, G, p, e_start, lead, ti, st); r != SN_OK) return r;
         }
-        e->pl_cout = c.pipe_cout;
-        e->pcount++;
-        e->pphase++;
+        pl.pl_cout = c.pipe_cout;
+        pl.launches++;
     }
     // behind this rollout's last k_play, on the caller's stream of THIS call:
     // the next call (or sn_pipe_sync) orders behind it without touching a
     // stream the caller may have destroyed since (one record per rollout)
-    HIP_TRY(hipEventRecord(e->ev_play, st));
+    HIP_TRY(hipEventRecord(pl.ev_play, st));
     return SN_OK;
 }
 
+// Every rollout and step goes through here.  Pipelined where it applies; else a
+// ring-fed (numpy-MT, in-kernel DrunkHamster) rollout runs in launches of
+// at most chunk_steps env-steps, each behind its own k_mt_prep, so that one
+// ring covers a launch's draws (a 4-player episode: 193.5 +- 9.3 words).
 static sn_status launch_play(sn_env* e, PlayArgs a, hipStream_t st) {
     const DevState& s = e->s;
+    const bool numpy = s.rng_mode == SN_RNG_NUMPY_MT;
+    a.vec_out = ((((uintptr_t)a.rewards) & 15) == 0) && ((((uintptr_t)a.actions_out) & 3) == 0);
     if (s.lg_K) {  // tournament handles: in-kernel DrunkHamster seats, pipelined numpy-MT or philox
         if (a.actions) return fail(SN_EUNSUPPORTED, "a tournament handle plays in-kernel DrunkHamster seats only (sn_rollout)");
         if (!(a.flags & SN_AUTO_RESET)) return fail(SN_EINVAL, "a tournament handle rolls out with SN_AUTO_RESET");
-        if (s.rng_mode == SN_RNG_NUMPY_MT) {
-            int wave;
-            if (!e->pipe || e->pipe_gpw != 64 || pipe_lds(s, a, 64, &wave) > (size_t)kLdsBytes)
-                return fail(SN_EUNSUPPORTED, "tournament rollouts need the pipelined numpy-MT path (64 games per wave)");
-            return launch_pipe(e, a, st);
-        }
-        return launch_play_one(e, a, st);
     }
-    if (s.rng_mode == SN_RNG_NUMPY_MT && !a.actions && e->pipe) {
-        int wave;
-        if (pipe_lds(s, a, e->pipe_gpw, &wave) <= (size_t)kLdsBytes) return launch_pipe(e, a, st);
+    if (numpy && !a.actions && (e->opt.pipe || s.lg_K)) {
+        const LdsPlan plan = lds_plan(s.N, obs_staged(a.obs, a.obs_stride), RNG_NUMPY_PIPE, e->opt.pipe_gpw);
+        const bool fits = block_lds(plan) <= (size_t)kLdsBytes;
+        if (s.lg_K && (!e->opt.pipe || e->opt.pipe_gpw != 64 || !fits))
+            return fail(SN_EUNSUPPORTED, "tournament rollouts need the pipelined numpy-MT path (64 games per wave)");
+        if (fits) return launch_pipe(e, a, plan, st);
     }
-    {
-        const sn_status r = sn_pipe_sync(e, st);
-        if (r != SN_OK) return r;
-    }
-    const bool ring = (s.rng_mode == SN_RNG_NUMPY_MT) && !a.actions && s.ring_w > 0;
-    if (!ring || a.steps <= e->chunk_steps) return launch_play_one(e, a, st);
-    const int64_t B = s.B, N = s.N;
-    for (int t0 = 0; t0 < a.steps; t0 += e->chunk_steps) {
-        PlayArgs c = a;
-        c.steps = min(e->chunk_steps, a.steps - t0);
-        if (a.rewards) c.rewards = a.rewards + (int64_t)t0 * B * N;
-        if (a.done) c.done = a.done + (int64_t)t0 * B;
-        if (a.actions_out) c.actions_out = a.actions_out + (int64_t)t0 * B * N;
-        if (a.obs) c.obs = a.obs + (int64_t)t0 * B * N * a.obs_stride;
-        const sn_status r = launch_play_one(e, c, st);
+    if (const sn_status r = sn_pipe_sync(e, st); r != SN_OK) return r;
+    const bool ring = numpy && !a.actions && s.ring_w > 0;
+    const int chunk = ring ? e->opt.chunk_steps : a.steps;  // only a ring limits a launch's draws
+    for (int t0 = 0; t0 < a.steps; t0 += chunk) {
+        const sn_status r = launch_play_one(e, slice_steps(a, t0, min(chunk, a.steps - t0), s.B, s.N), st);
         if (r != SN_OK) return r;
     }
     return SN_OK;
 }
+
 
 sn_status sn_step(sn_env* e, const int32_t* actions, int32_t* rewards, uint8_t* done, int32_t* invalid, int flags,
                   void* stream) {
@@ -2382,20 +2398,12 @@ sn_status sn_rollout(sn_env* e, int steps, int32_t* rewards, uint8_t* done, uint
     if (steps < 0) return fail(SN_EINVAL, "steps must be >= 0");
     const int L = (flags & SN_NO_SUMMARIES) ? 35 : 47;
     if (obs && (obs_stride < L || (obs_stride & 3))) return fail(SN_EINVAL, "obs_stride must be a multiple of 4 and >= obs length");
-    if (obs && (((uintptr_t)obs) & 3)) return fail(SN_EINVAL, "obs must be 4-byte aligned");
+    if (check_obs_align(obs, obs_stride) != SN_OK) return SN_EINVAL;
     if (steps == 0) return SN_OK;
     if (e->perr_host && __atomic_load_n(e->perr_host, __ATOMIC_RELAXED))
         return fail(SN_ERNG, "a pipelined numpy-MT draw ran past the twisted words; this handle's rollouts are invalid "
                              "from that launch on (sn_pipe_errors)");
-    PlayArgs a{};
-    a.steps = steps;
-    a.flags = flags;
-    a.obs_stride = obs_stride;
-    a.rewards = rewards;
-    a.done = done;
-    a.actions_out = actions;
-    a.obs = obs;
-    const sn_status r = launch_play(e, a, (hipStream_t)stream);
+    const sn_status r = launch_play(e, rollout_args(steps, flags, obs_stride, rewards, done, actions, obs), (hipStream_t)stream);
     if (r == SN_OK && e->s.lg_K) e->lg_phase = (e->lg_phase + steps) % kHand;
     e->phase = (r == SN_OK && e->phase >= 0 && (flags & SN_AUTO_RESET)) ? (e->phase + steps) % kHand : -1;
     return r;
@@ -2436,17 +2444,11 @@ sn_status sn_league_rollout(sn_env* e, int steps, int32_t* rewards, uint8_t* don
     if (steps % kHand) return fail(SN_EINVAL, "tournament rollouts play whole games (steps a multiple of 10)");
     if (steps < 0) return fail(SN_EINVAL, "steps must be >= 0");
     if (obs && (obs_stride < 47 || (obs_stride & 3))) return fail(SN_EINVAL, "obs_stride must be a multiple of 4 and >= 47");
+    if (check_obs_align(obs, obs_stride) != SN_OK) return SN_EINVAL;
     if (steps == 0) return SN_OK;
     if (e->perr_host && __atomic_load_n(e->perr_host, __ATOMIC_RELAXED))
         return fail(SN_ERNG, "a pipelined numpy-MT draw ran past the twisted words (sn_pipe_errors)");
-    PlayArgs a{};
-    a.steps = steps;
-    a.flags = SN_AUTO_RESET;
-    a.obs_stride = obs_stride;
-    a.rewards = rewards;
-    a.done = done;
-    a.actions_out = actions;
-    a.obs = obs;
+    PlayArgs a = rollout_args(steps, SN_AUTO_RESET, obs_stride, rewards, done, actions, obs);
     a.league_rec = records;
     return launch_play(e, a, (hipStream_t)stream);
 }

@@ -83,7 +83,9 @@ __host__ __device__ __forceinline__ int64_t ring16(uint32_t u, int64_t g, int64_
 // byte offset of stream position ri (mod kPipeRing) of game g
 __host__ __device__ __forceinline__ int64_t ring_byte(uint32_t ri, int64_t g, int64_t B) {
     return ring16(ri >> 4, g, B) * 16 + (ri & 15u);
-}constexpr int kPipeLead = 600;   // words k_mt_ahead keeps twisted ahead of the consumer (<= 624)
+}
+
+constexpr int kPipeLead = 600;   // words k_mt_ahead keeps twisted ahead of the consumer (<= 624)
 constexpr int kPipeWin = 240;    // of them, copied to LDS per lane at a k_play launch: a 4-player
                                   // episode draws 193.5 words, P(> 240) = 7e-6 per game (the rest come
                                   // from HBM); 304 -> 240 measured 7.46 -> 7.60 G env-steps/s interleaved
@@ -96,6 +98,11 @@ constexpr int kPipeWin = 240;    // of them, copied to LDS per lane at a k_play 
 // lead + 624 (g mod (depth + 1))), overshooting by at most a round less one
 // word.  The twisted end therefore never leads that consumer by more than
 constexpr int kTwistEveryMax = 5, kTwistDepthMax = 3;
+// Slots by launch index (launch_pipe, sechs_env.hip): the next writer of launch p-1's pabsc slot sits in a group behind
+// twist G, its reader (K + 3); a decode writes 2K + 1 episodes' records while a running launch reads one K back (3K + 1)
+static_assert((kPipeSlots & (kPipeSlots - 1)) == 0, "pabsc / ptend slots are taken mod kPipeSlots with a mask");
+static_assert(kPipeSlots >= kTwistEveryMax + 3, "no play launch overwrites a pabsc slot a running twist reads");
+static_assert(kDecRecords >= 3 * kTwistEveryMax + 1, "no decode overwrites a record a running play launch reads");
 constexpr int kPipeLeadMax = kPipeLead * (kTwistEveryMax + 1);                    // 3 600 (decode-ahead, K = 5)
 constexpr int kPipeSpanMax = kPipeLeadMax + kMtN * kTwistDepthMax + kMtN - 1;     // 6 095 words
 // and the ring, which a consumer reads from the 16-B unit holding its
@@ -148,17 +155,6 @@ struct RngOf<RNG_PHILOX, PF> {
     }
 };
 
-// numpy-MT words for k_play from the ring k_mt_prep filled just before the
-// launch: the low bytes of the next ring_w words of the game's stream, in
-// 16-B chunks interleaved over games (chunk q of game g at ring[q*B + g], so
-// a wave's lanes reading their q-th chunks read one contiguous 1-KB run).
-// LDS = true: the lane copies its ring to its LDS slot at launch start (16
-// coalesced loads per lane, one wait), so the step loop issues no global
-// loads at all -- a global load there would wait behind every observation
-// store still in flight (vmcnt counts loads and stores in issue order).
-// LDS = false: chunks come from HBM, the next one prefetched.  A lane that
-// runs the ring dry continues with MtGen from the in-place state (rare: the
-// ring is sized for a launch's draws + ~6.5 sd).
 // Past the ring (rare): the next 8 words of the stream from the in-place
 // state -- `extra` twisted words first, then numpy's in-place twist of the
 // next 8 (T stays 8-aligned; a crossed round saves the old mt[0]).  Out of
@@ -456,7 +452,7 @@ __device__ __forceinline__ void shuffle_targets(RingPipe& rng, ByteBuf& buf, uin
 constexpr int kPipeSlot = ((kPipeWin + 15 + 15) / 16) * 16 + 8;
 
 // bytes of a lane's LDS ring slot (+8: odd 8-B stride, conflict-free ds_read_b64 rows)
-__host__ __device__ __forceinline__ int ring_lds_stride(int ring_w) { return ring_w + 8; }
+__host__ __device__ constexpr int ring_lds_stride(int ring_w) { return ring_w + 8; }
 
 template <int PF>
 struct RngOf<RNG_NUMPY_RING, PF> {
@@ -903,38 +899,39 @@ inline unsigned grid_for(int64_t n) { return (unsigned)((n + kBlock - 1) / kBloc
 struct sn_env {
     int device;
     int cus;          // compute units of `device` (persistent grids size by it)
-    int chunk_steps;  // SN_OPT_CHUNK_STEPS
-    int pipe;         // SN_OPT_PIPELINE
-    int pipe_gpw;     // SN_OPT_PIPE_GPW: games per k_play wave on the pipelined path (32 or 64)
-    int pipe_lead;    // SN_OPT_PIPE_LEAD: words k_mt_ahead keeps twisted ahead (kPipeLead; tests lower it)
     int lg_phase;     // tournament handle: env-steps since the games were dealt, mod 10 (-1: not dealt yet)
     int lg_kind[16];  // tournament handle: per agent SN_AGENT_* (sn_league_agents; all RANDOM by default)
     int lg_mpc[16], lg_mmax[16];  // MCSAgent agents: mc_per_card, mc_max
     int phase;        // every game's env-steps since its deal, mod 10, when they are in lockstep; -1 unknown
-    int play_split;   // SN_OPT_PLAY_SPLIT: role-split k_play for lockstep DrunkHamster rollouts
-    int twist_every;  // SN_OPT_TWIST_EVERY: a k_mt_ahead beside every K-th play launch (K = 1 .. 5)
-    int tw_out;       // pipeline: ptend slot of the last twist
-    uint64_t pphase;  // pipeline: play launches since it started
-    int twist_round;  // SN_OPT_TWIST_ROUND: k_mt_ahead twists whole MT rounds (8 instead of 12 B of MT traffic per word)
-    int pipe_serial;  // SECHS_PIPE_SERIAL=1 (diagnostics): each twist waits for the play launch before it (no overlap)
-    int pl_cout;      // pabsc slot the last play launch wrote
-    int pK;           // SN_OPT_TWIST_EVERY of the running pipeline
-    hipEvent_t evt[2];  // after twist G, slot G mod 2
-    int twist_skip;   // SN_OPT_TWIST_SKIP (tests only): steady twists after the first group twist nothing
-    int twist_depth;  // SN_OPT_TWIST_DEPTH: extra whole rounds a refilling game twists past the lead (0 .. kTwistDepthMax)
-    int pipe_dec;     // SN_OPT_PIPE_DEC: decode-ahead (k_decode + k_play<RNG_NUMPY_DEC>) where it applies
-    int pdec;         // the running pipeline decodes ahead
-    int64_t dec_e;    // decode-ahead: episodes the play launches finished since the pipeline start
-    int64_t dec_next; // decode-ahead: the next episode k_decode will decode
+    struct Options {  // sn_set_option values (defaults: sn_create)
+        int chunk_steps;  // SN_OPT_CHUNK_STEPS
+        int pipe;         // SN_OPT_PIPELINE
+        int pipe_gpw;     // SN_OPT_PIPE_GPW: games per k_play wave on the pipelined path (32 or 64)
+        int pipe_lead;    // SN_OPT_PIPE_LEAD: words k_mt_ahead keeps twisted ahead (kPipeLead; tests lower it)
+        int pipe_dec;     // SN_OPT_PIPE_DEC: decode-ahead (k_decode + k_play<RNG_NUMPY_DEC>) where it applies
+        int pipe_serial;  // SECHS_PIPE_SERIAL=1 (diagnostics): each twist waits for the play launch before it (no overlap)
+        int play_split;   // SN_OPT_PLAY_SPLIT: role-split k_play for lockstep DrunkHamster rollouts
+        int twist_every;  // SN_OPT_TWIST_EVERY: a k_mt_ahead beside every K-th play launch (K = 1 .. 5)
+        int twist_round;  // SN_OPT_TWIST_ROUND: k_mt_ahead twists whole MT rounds (8 instead of 12 B of MT traffic per word)
+        int twist_depth;  // SN_OPT_TWIST_DEPTH: extra whole rounds a refilling game twists past the lead (0 .. kTwistDepthMax)
+        int twist_skip;   // SN_OPT_TWIST_SKIP (tests only): steady twists after the first group twist nothing
+    } opt;
     sechs::DevState s;
     // pipelined twist-ahead (sechs_env.hip launch_pipe): a k_mt_ahead for the
     // next play launch may be in flight on `side` (ev_prep) after a rollout
-    int pvalid;         // ring + ptend/pabsc/ptp are the live RNG state (mt_pos is stale)
-    uint64_t pcount;    // pipelined play launches so far
-    hipStream_t side;
-    hipStream_t side2;                      // decode-ahead: k_decode, concurrent with the twists on `side`
-    hipEvent_t evd[2], ev_prep2;            // after decode G (slot G mod 2); behind side2 (sn_pipe_sync)
-    hipEvent_t ev_prep, ev_main, ev_play;  // ev_play: after the last pipelined k_play (recorded on that call's stream)
+    struct Pipeline {
+        int valid;         // ring + ptend/pabsc/ptp are the live RNG state (mt_pos is stale)
+        int K, dec;        // the running pipeline's SN_OPT_TWIST_EVERY; it decodes ahead
+        uint64_t launches; // play launches since it started
+        int tw_out;        // ptend slot of the last twist
+        int pl_cout;       // pabsc slot the last play launch wrote
+        int64_t dec_e;     // decode-ahead: episodes the play launches finished since the pipeline start
+        int64_t dec_next;  // decode-ahead: the next episode k_decode will decode
+        hipStream_t side, side2;               // the twists; decode-ahead: k_decode, concurrent with them
+        hipEvent_t evt[2];                     // after twist G, slot G mod 2
+        hipEvent_t evd[2], ev_prep2;           // after decode G (slot G mod 2); behind side2 (sn_pipe_sync)
+        hipEvent_t ev_prep, ev_main, ev_play;  // ev_play: after the last pipelined k_play (recorded on that call's stream)
+    } pl;
     uint32_t* perr_host;                    // pinned, device-mapped mirror of s.perr (PlayArgs::perr_mirror)
     uint32_t* perr_host_dev;
     uint32_t* hbuf;      // one-game fast path (sn_step1 / sn_reset1): pinned, device-mapped exchange words

@@ -3,6 +3,7 @@
 Bit-exact for everything (integer/index work): rewards, done flags,
 actions, observations, hands, board, scores, RNG streams.
 """
+import ctypes
 import json
 import os
 
@@ -663,6 +664,131 @@ def test_pipelined_full_size_across_streams():
             assert np.array_equal(acts[:, idx[j]], ra[:, 0]), (e, j)
     torch.cuda.synchronize()
     assert env.pipe_errors() == 0
+
+
+_STRIDE_VARIANTS = {
+    "philox-split": ("philox", dict(play_split=1)),
+    "philox-nosplit": ("philox", dict(play_split=0)),
+    "numpy-lazy": ("numpy", dict(pipeline=0, ring_words=0)),
+    "numpy-ring256": ("numpy", dict(pipeline=0, ring_words=256)),
+    "numpy-ring512": ("numpy", dict(pipeline=0, ring_words=512)),
+    "numpy-dec": ("numpy", dict(pipe_dec=1)),
+    "numpy-pipe": ("numpy", dict(pipe_dec=0)),
+    "numpy-gpw32": ("numpy", dict(pipe_gpw=32)),
+}
+_STRIDE_B, _STRIDE_T, _STRIDE_SEED = 300, 13, 77  # a ragged last wave; 13 steps cross a deal, in two launches
+_stride_refs = {}
+
+
+def _stride_ref(rng, N):
+    """the oracle's 13 steps from the reset, computed once per (rng, N) and only read"""
+    if (rng, N) not in _stride_refs:
+        ref = O.VecOracle(_STRIDE_B, N, rng_mode=RNG[rng], seed=_STRIDE_SEED)
+        ref.reset()
+        _stride_refs[(rng, N)] = ref.rollout(_STRIDE_T, want_obs=True)
+    return _stride_refs[(rng, N)]
+
+
+@pytest.mark.parametrize("variant", list(_STRIDE_VARIANTS))
+@pytest.mark.parametrize("stride", [52, 64])
+@pytest.mark.parametrize("N", [4, 5])
+def test_obs_strides_match_oracle(N, stride, variant):
+    """observation rows wider than 48 bytes leave without the LDS staging
+    (play_steps' row-by-row branch; the launches size their LDS without the
+    staging area) on every play path: the same games as the oracle's, the
+    rows zero past the 47 observation bytes.  N = 5: an odd piece count, the
+    staging area larger than the deck area."""
+    rng, opts = _STRIDE_VARIANTS[variant]
+    env = venv(_STRIDE_B, N, seed=_STRIDE_SEED, rng=rng)
+    env.set_option(**opts)
+    env.reset()
+    out = env.rollout(_STRIDE_T, want_actions=True, want_obs=True, obs_stride=stride)
+    torch.cuda.synchronize()
+    rr, rd, ra, ro = _stride_ref(rng, N)
+    assert out["obs"].shape[-1] == stride
+    assert np.array_equal(out["actions"].cpu().numpy(), ra)
+    assert np.array_equal(out["rewards"].cpu().numpy(), rr)
+    assert np.array_equal(out["done"].cpu().numpy(), rd)
+    o = out["obs"].cpu().numpy()
+    assert np.array_equal(o[..., :47], ro)
+    assert not o[..., 47:].any()
+    if rng == "numpy":
+        assert env.pipe_errors() == 0
+    env.close()
+
+
+def _league_steps_oracle(B, K, lo, hi, seed, T):
+    """the first T env-steps of a DrunkHamster tournament handle (oracle.league_records' loop,
+    step by step): rewards [T, B, hi] (0 past the game's k seats), done [T, B], actions, k per step"""
+    rew = np.zeros((T, B, hi), dtype=np.int32)
+    done = np.zeros((T, B), dtype=np.uint8)
+    act = np.zeros((T, B, hi), dtype=np.uint8)
+    ks = np.zeros((T, B), dtype=np.int64)
+    for j in range(B):
+        rng = O.Rng(O.RNG_NUMPY_MT, seed + j)
+        g = None
+        for t in range(T):
+            if g is None or g.done():
+                k = lo + rng.interval(hi - lo)
+                rng.shuffle(np.arange(K))
+                g = O.Game(k)
+                g.reset(rng)
+            acts = [g.random_action(rng, p) for p in range(k)]
+            bad, r = g.step(acts)
+            assert bad < 0
+            rew[t, j, :k], act[t, j, :k], done[t, j], ks[t, j] = r, acts, g.done(), k
+    return rew, done, act, ks
+
+
+@pytest.mark.parametrize("kind", ["numpy", "philox", "tournament"])
+def test_rollout_rejects_misaligned_stride48_obs(kind):
+    """48-byte observation rows are staged through LDS and leave as 16-byte
+    pieces, so sn_rollout / sn_league_rollout refuse a stride-48 obs that is
+    not 16-byte aligned (SN_EINVAL) -- before anything is launched and before
+    any handle state moves: the aligned rollout after it equals the oracle's
+    from the reset."""
+    from rl_6_nimmt import _native as nat
+
+    B, N, T, seed = 64, 4, 13, 9
+    rng = "philox" if kind == "philox" else "numpy"
+    env = venv(B, N, seed=seed, rng=rng)
+    if kind == "tournament":
+        nat.check(nat.lib().sn_league_config(env._h, 5, 2, 4), "sn_league_config")
+    env.reset()
+    buf = torch.zeros(T * B * N * 48 + 16, dtype=torch.int8, device=env.device)
+    view = buf[4: 4 + T * B * N * 48].view(T, B, N, 48)
+    assert view.data_ptr() % 16 == 4
+    with pytest.raises(ValueError, match="16-byte aligned"):
+        env.rollout(T, out={"obs": view})
+    if kind == "tournament":
+        rec = torch.zeros((1, B, 1 + N), dtype=torch.int32, device=env.device)
+        with pytest.raises(ValueError, match="16-byte aligned"):
+            nat.check(nat.lib().sn_league_rollout(env._h, 10, None, None, None, nat.ptr(view), 48, nat.ptr(rec),
+                                                  env._stream()), "sn_league_rollout")
+        with pytest.raises(ValueError, match="4-byte aligned"):
+            nat.check(nat.lib().sn_league_rollout(env._h, 10, None, None, None, ctypes.c_void_p(buf.data_ptr() + 2), 52, nat.ptr(rec),
+                                                  env._stream()), "sn_league_rollout")
+    torch.cuda.synchronize()
+    assert not buf.any()  # nothing was written
+    out = env.rollout(T, want_actions=True, want_obs=True)
+    torch.cuda.synchronize()
+    if kind == "tournament":
+        rr, rd, ra, ks = _league_steps_oracle(B, 5, 2, 4, seed, T)
+        present = np.arange(N)[None, None, :] < ks[..., None]
+        assert np.array_equal(out["rewards"].cpu().numpy(), rr)
+        assert np.array_equal(out["done"].cpu().numpy(), rd)
+        assert np.array_equal(np.where(present, out["actions"].cpu().numpy(), 0), ra)
+    else:
+        ref = O.VecOracle(B, N, rng_mode=RNG[rng], seed=seed)
+        ref.reset()
+        rr, rd, ra, ro = ref.rollout(T, want_obs=True)
+        assert np.array_equal(out["actions"].cpu().numpy(), ra)
+        assert np.array_equal(out["rewards"].cpu().numpy(), rr)
+        assert np.array_equal(out["done"].cpu().numpy(), rd)
+        assert np.array_equal(out["obs"].cpu().numpy()[..., :47], ro)
+    if rng == "numpy":
+        assert env.pipe_errors() == 0
+    env.close()
 
 
 _DEBUG_WORKLOAD = r"""
