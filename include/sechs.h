@@ -551,6 +551,69 @@ sn_status sn_per_update(sn_per* per, int64_t n, const uint32_t* tree_idx, const 
                         double upper, double alpha, void* stream);
 /* the 2*capacity-1 nodes (tests, cloning) */
 sn_status sn_per_tree(sn_per* per, double* tree_out, void* stream);
+/* The payload rows of n data slots (slots [n] int32 in device memory, slot =
+   leaf - capacity + 1) into rows_out [n][row_bytes], 16-byte aligned: the
+   gather of sn_per_sample without the tree walk.  A slot outside
+   [0, capacity) yields a zero row.  This is the uniform replay of DQNVanilla /
+   DDQNAgent: History.sample (replay_buffer.py:233-234) draws
+   random.sample(range(len)), the caller draws the slots. */
+sn_status sn_per_gather(sn_per* per, int64_t n, const int32_t* slots, void* rows_out, void* stream);
+
+/* ---- Batched DQN family (agents/dqn.py:42-231,304-380,427) ---------------
+   Every deciding seat of every game acts together; decisions are addressed
+   through sn_puct exactly as sn_policy_sample's (seats_mask, or dec_list /
+   num_dec, plus n, seed, step).  The Q net, MultiHeadedMLP(47, hidden,
+   (104,)), runs between the calls in PyTorch-ROCm.
+
+   sn_dqn_obs: the observation a DQN agent acts on, the raw _create_states row
+   (env.py:174-212; GameSession hands it over un-normalised).  obs_i8 [D][48]
+   int8 = the 47 values and one zero pad byte (the replay payload form);
+   states [D][48] f32 (bf16 = 0) or bf16 (bf16 = 1) = the same values as
+   floats, column 47 zero (every value lies in -1..104, so bf16 holds it
+   exactly).  Either output may be NULL; both 16-byte aligned.  In a
+   tournament game of k < N players field 10 (the player count) is k, as in
+   sn_puct_root_rows.  q->n is not used, and 0 is accepted: after a game's
+   last step the hand is empty and the row is the terminal next_state. */
+sn_status sn_dqn_obs(sn_env* env, const sn_puct* q, void* obs_i8, void* states, int bf16, void* stream);
+/* _action_selection (agents/dqn.py:196-217): epsilon-greedy over the hand.
+   qvals [D][q_stride] f32, q_stride >= 104: the Q head over all 104 cards.
+   Per decision two Philox uniforms u1, u2 keyed like sn_policy_sample's
+   (q->seed ^ q->step, game, seat) under a rollout tag of their own.  Greedy
+   when u1 > eps: action = legal[k], k the first maximum of Q[legal[j]] over
+   the ascending legal list (numpy's first arg-max of the -1e8-masked vector
+   for any Q > -1e8), value = Q[action]; else action = legal[floor(u2 * n)],
+   value = -1.  eps <= 0 never explores, eps >= 1 always does.  actions
+   [B][N] int32 (deciding seats only), index [D] = k, value [D] f32; index
+   and value may be NULL. */
+sn_status sn_dqn_select(sn_env* env, const sn_puct* q, const float* qvals, int64_t q_stride, double eps,
+                        int32_t* actions, int32_t* index, float* value, void* stream);
+/* The transitions of one episode as replay rows (the experience dicts of
+   DQNVanilla.learn, agents/dqn.py:87-108: state, action, reward, next_state,
+   done).  obs_i8 [T+1][D][48] (sn_dqn_obs before every step and after the
+   last), actions [T][D] int32 (stored as one byte), rewards_seen [T][D]
+   int32 -> rows [T*D][112], t-major then decider:
+     bytes 0-47 state = obs[t], 48-95 next_state = obs[t+1], 96 action (card),
+     97 done (1 only at t = T-1), 98 hand size at state, 99 zero,
+     100-103 reward int32, 104-111 zero.
+   obs_i8 and rows 16-byte aligned. */
+sn_status sn_dqn_pack(int64_t T, int64_t D, const void* obs_i8, const int32_t* actions, const int32_t* rewards_seen,
+                      void* rows, void* stream);
+/* the inverse for n sampled rows (_prep_minibatch, agents/dqn.py:143-168):
+   states, next_states [n][48] f32, action [n] int64, reward [n] f32,
+   not_done [n] f32 = 1 - done.  Each output may be NULL. */
+sn_status sn_dqn_unpack(int64_t n, const void* rows, float* states, float* next_states, int64_t* action,
+                        float* reward, float* not_done, void* stream);
+/* Both Bellman targets over q_next_local / q_next_target [n][stride] f32
+   (stride >= 104; the maximum runs over all 104 actions, unmasked, as in the
+   reference).  q_next_target NULL: DQNVanilla._calc_reward
+   (agents/dqn.py:182-194) = reward + gamma * (max_a Q_local(s') * not_done);
+   else DDQNAgent._calc_reward (agents/dqn.py:323-340) = reward + gamma *
+   (Q_target(s')[argmax_a Q_local(s')] * not_done), the lowest index on ties.
+   fp32 in exactly that operation order, unfused; gamma is rounded to f32
+   once, as torch rounds the Python scalar: bit-equal to the torch fp32
+   expression on the same tensors. */
+sn_status sn_dqn_target(int64_t n, const float* q_next_local, const float* q_next_target, int64_t stride,
+                        const float* reward, const float* not_done, double gamma, float* target, void* stream);
 
 #ifdef __cplusplus
 }

@@ -1314,6 +1314,189 @@ __global__ void k_policy_sample(DevState s, PuctArgs a, const float* logits, int
     if (entropy) entropy[d] = lse - sx / sum;  // -sum p log p
 }
 
+// ---------------------------------------------------------------- batched DQN (rl_6_nimmt/dqn.py)
+constexpr int kDqnObs = 48;       // observation bytes per row: 47 values + one zero pad
+constexpr int kDqnActions = 104;  // the Q head: one value per card
+constexpr int kDqnRow = 112;      // replay payload row (the layout at sn_dqn_pack, include/sechs.h)
+constexpr int kDqnPieces = kDqnRow / 16;
+
+// byte i (0..15) of a 16-byte piece as the int8 it holds
+__device__ __forceinline__ float piece_val(const u32x4& v, int i) {
+    const uint32_t w = (i >> 2) == 0 ? v.x : (i >> 2) == 1 ? v.y : (i >> 2) == 2 ? v.z : v.w;
+    return (float)(int8_t)((w >> (8 * (i & 3))) & 0xFFu);
+}
+__device__ __forceinline__ void piece_to_f32(const u32x4& v, float* dst) {
+#pragma unroll
+    for (int j = 0; j < 4; j++)
+        reinterpret_cast<float4*>(dst)[j] =
+            float4{piece_val(v, 4 * j), piece_val(v, 4 * j + 1), piece_val(v, 4 * j + 2), piece_val(v, 4 * j + 3)};
+}
+// the values are integers in -1..104: their bf16 is the upper half of the f32, exactly
+__device__ __forceinline__ uint32_t bf16_pair(float a, float b) {
+    return (__float_as_uint(a) >> 16) | (__float_as_uint(b) & 0xFFFF0000u);
+}
+__device__ __forceinline__ void piece_to_bf16(const u32x4& v, uint16_t* dst) {
+#pragma unroll
+    for (int j = 0; j < 2; j++)
+        reinterpret_cast<u32x4*>(dst)[j] = u32x4{bf16_pair(piece_val(v, 8 * j), piece_val(v, 8 * j + 1)),
+                                                 bf16_pair(piece_val(v, 8 * j + 2), piece_val(v, 8 * j + 3)),
+                                                 bf16_pair(piece_val(v, 8 * j + 4), piece_val(v, 8 * j + 5)),
+                                                 bf16_pair(piece_val(v, 8 * j + 6), piece_val(v, 8 * j + 7))};
+}
+
+// The observation a DQN agent acts on: the raw _create_states row
+// (env.py:174-212) of every deciding seat, un-normalised, as the int8
+// replay form and as the Q net's float input (column 47 zero).  One lane
+// per decision; an empty hand (after the last step) is the terminal
+// next_state: ten -1 bytes.
+template <bool BF16>
+__global__ void k_dqn_obs(DevState s, PuctArgs a, u32x4* obs_i8, void* states) {
+    const int64_t d = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (d >= a.D) return;
+    int64_t g;
+    int p;
+    dec_to_gp(a, d, g, p);
+    const Hand h = load_hand(s, p, g);
+    uint32_t w2hi;
+    const GameWords gw = game_words<true>(players_of(a, g), load_board(s, g), w2hi);
+    const u32x4 row[3] = {u32x4{(uint32_t)h.lo, (uint32_t)(h.lo >> 32), (h.hi & 0xFFFFu) | w2hi, gw.w0}, gw.a, gw.b};
+    if (obs_i8) {
+#pragma unroll
+        for (int c = 0; c < 3; c++) obs_i8[d * 3 + c] = row[c];
+    }
+    if (states) {
+#pragma unroll
+        for (int c = 0; c < 3; c++) {
+            if (BF16)
+                piece_to_bf16(row[c], (uint16_t*)states + d * kDqnObs + 16 * c);
+            else
+                piece_to_f32(row[c], (float*)states + d * kDqnObs + 16 * c);
+        }
+    }
+}
+
+// _action_selection (agents/dqn.py:85-101) for every deciding seat: epsilon-
+// greedy over the hand.  qvals [D][q_stride] f32, the Q head over all 104
+// cards.  Two Philox uniforms keyed as k_policy_sample's (seed ^ step, game,
+// seat) with the rollout tag 0xFFFFE, so the streams never meet that
+// kernel's (0xFFFFF) or a PUCT rollout's.  Greedy: the first maximum of
+// Q[legal[j]] over the ascending legal list = numpy's first arg-max of the
+// -1e8-masked vector (any Q > -1e8).  One lane per decision.
+__global__ void k_dqn_select(DevState s, PuctArgs a, const float* qvals, int64_t q_stride, double eps, int32_t* actions,
+                             int32_t* index, float* value) {
+    const int64_t d = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (d >= a.D) return;
+    int64_t g;
+    int p;
+    dec_to_gp(a, d, g, p);
+    const Hand h = load_hand(s, p, g);
+    const uint64_t gid = s.game_offset + (uint64_t)g;
+    const uint64_t stream = ((uint64_t)(uint32_t)gid << 32) | ((uint64_t)p << 28) | (0xFFFFEull << 8);
+    const u32x4 o = philox4x32_10(0u, 0u, (uint32_t)stream, (uint32_t)(stream >> 32), a.seed_lo ^ puct_step_of(a),
+                                  a.seed_hi);
+    const float u1 = (float)(o.x >> 8) * (1.0f / 16777216.0f), u2 = (float)(o.y >> 8) * (1.0f / 16777216.0f);
+    int k;
+    float v;
+    if (eps <= 0.0 || (eps < 1.0 && (double)u1 > eps)) {  // random.random() > eps; the ends never / always explore
+        const float* x = qvals + d * q_stride;
+        k = 0;
+        v = -1.f;
+        for (int j = 0; j < a.n; j++) {
+            const uint32_t c = hand_get(h, (uint32_t)j);
+            if (c >= (uint32_t)kDqnActions) break;  // a hand shorter than q->n: no load past the Q row
+            const float q = x[c];
+            if (j == 0 || q > v) v = q, k = j;
+        }
+    } else {  // random.choice(legal)
+        k = (int)(u2 * (float)a.n);
+        k = k < a.n ? k : a.n - 1;
+        v = -1.f;
+    }
+    actions[g * s.N + p] = (int32_t)hand_get(h, (uint32_t)k);
+    if (index) index[d] = k;
+    if (value) value[d] = v;
+}
+
+// Replay rows of one episode: row (t, d) = [obs[t][d] | obs[t+1][d] | action,
+// done, hand size, 0 | reward i32 | 0, 0].  One lane per 16-byte piece,
+// consecutive lanes on consecutive pieces of a row (as k_per_store).
+__global__ void k_dqn_pack(int64_t T, int64_t D, const u32x4* __restrict__ obs, const int32_t* __restrict__ actions,
+                           const int32_t* __restrict__ rewards_seen, u32x4* __restrict__ rows) {
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= T * D * kDqnPieces) return;
+    const int64_t r = e / kDqnPieces;
+    const int c = (int)(e - r * kDqnPieces);
+    const int64_t t = r / D;
+    u32x4 v;
+    if (c < 6) {
+        v = obs[(r + (c < 3 ? 0 : D)) * 3 + (c < 3 ? c : c - 3)];  // obs[t + 1][d] lies D rows on
+    } else {
+        const u32x4 h = obs[r * 3];  // hand bytes 0..9: the cards held are >= 0
+        const uint32_t neg = (h.x & 0x80808080u) | ((h.y & 0x80808080u) >> 1) | ((h.z & 0x00008080u) >> 2);
+        const uint32_t hand = 10u - (uint32_t)__builtin_popcount(neg);
+        const uint32_t done = t == T - 1 ? 1u : 0u;
+        v = u32x4{((uint32_t)actions[r] & 0xFFu) | (done << 8) | (hand << 16), (uint32_t)rewards_seen[r], 0u, 0u};
+    }
+    rows[e] = v;
+}
+
+// the inverse for a sampled minibatch: fp32 states / next_states [n][48],
+// action [n] i64, reward [n] f32, not_done [n] f32 = 1 - done.  One lane per
+// 16-byte piece of a row.
+__global__ void k_dqn_unpack(int64_t n, const u32x4* __restrict__ rows, float* __restrict__ states,
+                             float* __restrict__ next_states, int64_t* __restrict__ action, float* __restrict__ reward,
+                             float* __restrict__ not_done) {
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= n * kDqnPieces) return;
+    const int64_t r = e / kDqnPieces;
+    const int c = (int)(e - r * kDqnPieces);
+    const u32x4 v = rows[e];
+    if (c < 3) {
+        if (states) piece_to_f32(v, states + r * kDqnObs + 16 * c);
+    } else if (c < 6) {
+        if (next_states) piece_to_f32(v, next_states + r * kDqnObs + 16 * (c - 3));
+    } else {
+        if (action) action[r] = (int64_t)(v.x & 0xFFu);
+        if (reward) reward[r] = (float)(int32_t)v.y;
+        if (not_done) not_done[r] = ((v.x >> 8) & 0xFFu) ? 0.f : 1.f;
+    }
+}
+
+// Bellman targets (agents/dqn.py:136-140 DQNVanilla._calc_reward, :165-174
+// DDQNAgent._calc_reward): one wave per row, lanes on consecutive actions,
+// an arg-max butterfly that carries the index (lowest index on ties, as
+// torch.max / torch.argmax over the unmasked 104 actions).  fp32 in torch's
+// operation order -- reward + gamma * (value * not_done) -- unfused.
+__global__ __launch_bounds__(kBlock) void k_dqn_target(int64_t n, const float* __restrict__ q_local,
+                                                       const float* __restrict__ q_target, int64_t stride,
+                                                       const float* __restrict__ reward,
+                                                       const float* __restrict__ not_done, float gamma,
+                                                       float* __restrict__ target) {
+#pragma clang fp contract(off)
+    const int lane = (int)(threadIdx.x & 63u);
+    const int64_t r = (int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
+    if (r >= n) return;  // whole waves leave together
+    const float* x = q_local + r * stride;
+    float v = x[lane];
+    int i = lane;
+    if (lane + 64 < kDqnActions) {
+        const float w = x[lane + 64];
+        if (w > v) v = w, i = lane + 64;
+    }
+#pragma unroll
+    for (int m = 32; m > 0; m >>= 1) {
+        const float ov = __shfl_xor(v, m, 64);
+        const int oi = __shfl_xor(i, m, 64);
+        if (ov > v || (ov == v && oi < i)) v = ov, i = oi;
+    }
+    if (lane == 0) {
+        const float best = q_target ? q_target[r * stride + i] : v;
+        const float kept = best * not_done[r];
+        const float disc = gamma * kept;
+        target[r] = reward[r] + disc;
+    }
+}
+
 // test hook for the formula fixtures (F5): stats/hist/probs given per decision
 __global__ void k_puct_score(int64_t D, int n_max, const int32_t* n, const int32_t* stats, const int32_t* hist,
                              const float* probs, double c_puct, double* pucts, int32_t* choice) {
@@ -1575,6 +1758,74 @@ sn_status sn_policy_sample(sn_env* e, const sn_puct* q, const float* logits, int
     if (st != SN_OK) return st;
     hipLaunchKernelGGL(k_policy_sample, dim3(grid_for(a.D)), dim3(kBlock), 0, (hipStream_t)stream, e->s, a, logits,
                        actions, index, log_prob, entropy);
+    HIP_TRY(hipGetLastError());
+    return SN_OK;
+}
+
+sn_status sn_dqn_obs(sn_env* e, const sn_puct* q, void* obs_i8, void* states, int bf16, void* stream) {
+    if (!q) return set_error(SN_EINVAL, "NULL argument");
+    if ((((uintptr_t)obs_i8 | (uintptr_t)states) & 15) != 0) return set_error(SN_EINVAL, "outputs must be 16-byte aligned");
+    sn_puct qq = *q;
+    if (qq.n == 0) qq.n = 1;  // the hand size is not used: after the last step it is 0
+    PuctArgs a{};
+    sn_status st = puct_args(e, &qq, a);
+    if (st != SN_OK) return st;
+    if (!obs_i8 && !states) return SN_OK;
+    if (bf16)
+        hipLaunchKernelGGL(k_dqn_obs<true>, dim3(grid_for(a.D)), dim3(kBlock), 0, (hipStream_t)stream, e->s, a,
+                           (u32x4*)obs_i8, states);
+    else
+        hipLaunchKernelGGL(k_dqn_obs<false>, dim3(grid_for(a.D)), dim3(kBlock), 0, (hipStream_t)stream, e->s, a,
+                           (u32x4*)obs_i8, states);
+    HIP_TRY(hipGetLastError());
+    return SN_OK;
+}
+
+sn_status sn_dqn_select(sn_env* e, const sn_puct* q, const float* qvals, int64_t q_stride, double eps, int32_t* actions,
+                        int32_t* index, float* value, void* stream) {
+    if (!qvals || !actions) return set_error(SN_EINVAL, "NULL argument");
+    if (q_stride < kDqnActions) return set_error(SN_EINVAL, "q_stride must be >= 104");
+    if (!(eps == eps)) return set_error(SN_EINVAL, "eps is NaN");
+    PuctArgs a{};
+    sn_status st = puct_args(e, q, a);
+    if (st != SN_OK) return st;
+    hipLaunchKernelGGL(k_dqn_select, dim3(grid_for(a.D)), dim3(kBlock), 0, (hipStream_t)stream, e->s, a, qvals,
+                       q_stride, eps, actions, index, value);
+    HIP_TRY(hipGetLastError());
+    return SN_OK;
+}
+
+sn_status sn_dqn_pack(int64_t T, int64_t D, const void* obs_i8, const int32_t* actions, const int32_t* rewards_seen,
+                      void* rows, void* stream) {
+    if (!obs_i8 || !actions || !rewards_seen || !rows) return set_error(SN_EINVAL, "NULL argument");
+    if (T < 1 || D < 1 || T > 0x7FFFFFFF / D) return set_error(SN_EINVAL, "T x D must be in 1..2^31-1");
+    if ((((uintptr_t)obs_i8 | (uintptr_t)rows) & 15) != 0) return set_error(SN_EINVAL, "obs_i8 and rows must be 16-byte aligned");
+    hipLaunchKernelGGL(k_dqn_pack, dim3(grid_for(T * D * kDqnPieces)), dim3(kBlock), 0, (hipStream_t)stream, T, D,
+                       (const u32x4*)obs_i8, actions, rewards_seen, (u32x4*)rows);
+    HIP_TRY(hipGetLastError());
+    return SN_OK;
+}
+
+sn_status sn_dqn_unpack(int64_t n, const void* rows, float* states, float* next_states, int64_t* action, float* reward,
+                        float* not_done, void* stream) {
+    if (!rows) return set_error(SN_EINVAL, "NULL argument");
+    if (n < 1 || n > 0x7FFFFFFF) return set_error(SN_EINVAL, "n must be in 1..2^31-1");
+    if ((((uintptr_t)rows | (uintptr_t)states | (uintptr_t)next_states) & 15) != 0)
+        return set_error(SN_EINVAL, "rows, states and next_states must be 16-byte aligned");
+    hipLaunchKernelGGL(k_dqn_unpack, dim3(grid_for(n * kDqnPieces)), dim3(kBlock), 0, (hipStream_t)stream, n,
+                       (const u32x4*)rows, states, next_states, action, reward, not_done);
+    HIP_TRY(hipGetLastError());
+    return SN_OK;
+}
+
+sn_status sn_dqn_target(int64_t n, const float* q_next_local, const float* q_next_target, int64_t stride,
+                        const float* reward, const float* not_done, double gamma, float* target, void* stream) {
+    if (!q_next_local || !reward || !not_done || !target) return set_error(SN_EINVAL, "NULL argument");
+    if (n < 1 || n > 0x7FFFFFFF) return set_error(SN_EINVAL, "n must be in 1..2^31-1");
+    if (stride < kDqnActions) return set_error(SN_EINVAL, "stride must be >= 104");
+    hipLaunchKernelGGL(k_dqn_target, dim3((unsigned)((n + kBlock / 64 - 1) / (kBlock / 64))), dim3(kBlock), 0,
+                       (hipStream_t)stream, n, q_next_local, q_next_target, stride, reward, not_done, (float)gamma,
+                       target);
     HIP_TRY(hipGetLastError());
     return SN_OK;
 }

@@ -166,6 +166,22 @@ __global__ void __launch_bounds__(kPerBlock) k_per_sample(const double* __restri
     }
 }
 
+// The payload rows of n given data slots: k_per_sample's gather without the
+// tree walk (History.sample, replay_buffer.py: random.sample(range(len))
+// picks the slots).  A slot outside [0, cap) gives a zero row.
+__global__ void __launch_bounds__(kPerBlock) k_per_gather(const uint8_t* __restrict__ ring, int64_t cap, int64_t n,
+                                                          const int32_t* __restrict__ slots,
+                                                          uint8_t* __restrict__ rows_out, int chunks) {
+    const int64_t e = (int64_t)blockIdx.x * kPerBlock + threadIdx.x;
+    if (e >= n * chunks) return;
+    const int64_t s = e / chunks;
+    const int c = (int)(e - s * chunks);
+    const int64_t slot = slots[s];
+    uint4 v = uint4{0u, 0u, 0u, 0u};
+    if (slot >= 0 && slot < cap) v = reinterpret_cast<const uint4*>(ring)[slot * chunks + c];
+    reinterpret_cast<uint4*>(rows_out)[e] = v;
+}
+
 // batch_update (replay_buffer.py:188-200) is a sequential loop: where a tree
 // index repeats, the last position wins.  k_per_claim records per leaf the
 // highest position + 1 that names it (integer max: the result does not depend
@@ -322,6 +338,19 @@ sn_status sn_per_sample(sn_per* per, int64_t n, const double* u, double beta, ui
     k_per_sample<<<per_grid(n), kPerBlock, 0, st>>>(per->tree, per->ring, per->cap, n, u, beta, tree_idx, priority,
                                                     is_weight, (uint8_t*)rows_out,
                                                     rows_out ? (int)(per->row_bytes / 16) : 0, per->part, nparts);
+    HIP_TRY(hipGetLastError());
+    return SN_OK;
+}
+
+sn_status sn_per_gather(sn_per* per, int64_t n, const int32_t* slots, void* rows_out, void* stream) {
+    if (!per || !slots || !rows_out) return set_error(SN_EINVAL, "NULL argument");
+    if (per->row_bytes == 0) return set_error(SN_EINVAL, "gather from a replay without payload");
+    if (n < 1 || n > 0x7FFFFFFF) return set_error(SN_EINVAL, "n must be in 1..2^31-1");
+    if (((uintptr_t)rows_out & 15) != 0) return set_error(SN_EINVAL, "rows_out must be 16-byte aligned");
+    HIP_TRY(hipSetDevice(per->device));
+    const int chunks = (int)(per->row_bytes / 16);
+    k_per_gather<<<per_grid(n * chunks), kPerBlock, 0, (hipStream_t)stream>>>(per->ring, per->cap, n, slots,
+                                                                             (uint8_t*)rows_out, chunks);
     HIP_TRY(hipGetLastError());
     return SN_OK;
 }

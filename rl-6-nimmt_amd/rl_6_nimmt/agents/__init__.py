@@ -8,10 +8,10 @@ registry -- as in the reference).
 The DQN family's four base agents -- DQNVanilla ("dqn"), DDQNAgent ("ddqn"),
 DQN_PRBAgent ("dqn_prb"), DDQN_PRBAgent ("ddqn_prb") -- are drop-ins on the
 device prioritised replay (rl_6_nimmt/replay.py) and registered in
-DQN_AGENTS, not in AGENTS: every AGENTS entry has a batched-league engine,
-and the batched league DQN learner is not built yet (league.agent_kind raises
-NotImplementedError for them).  Not built: the duelling, noisy and n-step DQN
-variants and the human UI.
+DQN_AGENTS, not in AGENTS.  The batched league seats them through
+league.engine_kind -> "dqn" (dqn.BatchedDQN on the replay's payload ring);
+league.agent_kind, the registry's map, still raises NotImplementedError for
+them.  Not built: the duelling, noisy and n-step DQN variants and the human UI.
 """
 from .base import Agent
 from .random import DrunkHamster

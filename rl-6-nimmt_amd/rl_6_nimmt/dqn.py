@@ -1,0 +1,324 @@
+"""Batched DQN family on one MI355X: the engine that seats DQNVanilla,
+DDQNAgent, DQN_PRBAgent and DDQN_PRBAgent (agents/dqn.py; reference
+agents/dqn.py:42-231,304-380,427) in the batched league.
+
+Every deciding seat of every game acts together.  Per decision batch:
+    sn_dqn_obs     the raw _create_states rows (env.py:174-212), as int8 replay
+                   rows and as the Q net's float input
+    Q net          MultiHeadedMLP(47, hidden, (104,)) forward on PyTorch-ROCm
+                   (a device copy in net_dtype, its input weight padded with a
+                   zero column so the 48-wide rows go in unsliced)
+    sn_dqn_select  epsilon-greedy over the hand (_action_selection), Philox
+At the end of an episode sn_dqn_pack turns the staged observations, actions
+and rewards into 112-byte transition rows, stored in a DevicePER(capacity,
+112) -- for the uniform variants too: they draw slots and `gather`.
+
+Learning (`learn`, once per round): `updates` minibatches of `minibatch`
+rows; per minibatch sample / gather -> sn_dqn_unpack -> fp32 forwards of
+state and next_state on the agent's own module -> sn_dqn_target (both
+Bellman targets) -> loss -> (PER) priorities written back -> (DDQN) soft
+update of the target net every `retrain_interval` updates -> optimiser step.
+
+Kept from the reference: the reward a transition carries is the PREVIOUS
+step's (GameSession's one-step lag, play.py:29,57,72: r_0 = 0 and the last
+step's reward never reaches the agent; REINFORCE here keeps the same lag),
+done is set at the last step only, the length gate `len(replay) > minibatch`,
+the maximum over all 104 actions, unmasked, in the targets.
+Different by construction: exploration draws are Philox, not Python's
+`random` (parity unpinned, like the other engines' samplers), and a round
+trains on `updates` x `minibatch` rows, not 10 x 64 per game.
+
+`pack_rows_host`, `unpack_rows_host` and `bellman_target_host` are the torch
+models of the kernels (they run on any device); the tests hold the kernels
+to them.
+"""
+import copy
+
+import torch
+from torch import nn
+
+from . import _native as nat
+from .puct import BatchedPUCT, FusedMLP, ctypes_ref
+from .replay import DevicePER
+
+T_STEPS = 10
+OBS = 48  # 47 observation values + one zero pad
+NUM_ACTIONS = 104
+ROW_BYTES = 112
+OFF_STATE, OFF_NEXT_STATE, OFF_ACTION, OFF_DONE, OFF_HAND, OFF_REWARD = 0, 48, 96, 97, 98, 100
+
+
+# ---------------------------------------------------------------- host models of the kernels
+def pack_rows_host(obs, actions, rewards_seen):
+    """sn_dqn_pack in torch.  obs int8 [T+1, D, 47 or 48], actions [T, D],
+    rewards_seen [T, D] -> uint8 [T*D, 112], t-major then decider."""
+    obs = torch.as_tensor(obs).to(torch.int8)
+    actions, rewards_seen = torch.as_tensor(actions), torch.as_tensor(rewards_seen)
+    T, D = actions.shape
+    if obs.shape[-1] == OBS - 1:
+        obs = torch.cat((obs, torch.zeros_like(obs[..., :1])), dim=-1)
+    assert obs.shape == (T + 1, D, OBS)
+    rows = torch.zeros((T, D, ROW_BYTES), dtype=torch.uint8, device=obs.device)
+    rows[..., OFF_STATE: OFF_STATE + OBS] = obs[:-1].contiguous().view(torch.uint8)
+    rows[..., OFF_NEXT_STATE: OFF_NEXT_STATE + OBS] = obs[1:].contiguous().view(torch.uint8)
+    rows[..., OFF_ACTION] = actions.to(obs.device).to(torch.uint8)
+    rows[T - 1, :, OFF_DONE] = 1
+    rows[..., OFF_HAND] = (obs[:-1, :, :10] >= 0).sum(dim=-1).to(torch.uint8)
+    rew = rewards_seen.to(obs.device).to(torch.int32).contiguous()
+    rows[..., OFF_REWARD: OFF_REWARD + 4] = rew.view(torch.uint8).reshape(T, D, 4)  # little endian, as the GPU's
+    return rows.reshape(T * D, ROW_BYTES)
+
+
+def unpack_rows_host(rows):
+    """sn_dqn_unpack in torch: uint8 [n, 112] -> (states f32 [n, 48],
+    next_states f32 [n, 48], action int64 [n], reward f32 [n], not_done f32 [n])"""
+    rows = torch.as_tensor(rows).reshape(-1, ROW_BYTES)
+    states = rows[:, OFF_STATE: OFF_STATE + OBS].contiguous().view(torch.int8).float()
+    nxt = rows[:, OFF_NEXT_STATE: OFF_NEXT_STATE + OBS].contiguous().view(torch.int8).float()
+    action = rows[:, OFF_ACTION].to(torch.int64)
+    reward = rows[:, OFF_REWARD: OFF_REWARD + 4].contiguous().view(torch.int32).reshape(-1).float()
+    not_done = 1.0 - rows[:, OFF_DONE].float()
+    return states, nxt, action, reward, not_done
+
+
+def bellman_target_host(q_next_local, q_next_target, reward, not_done, gamma):
+    """sn_dqn_target in torch (fp32): DQNVanilla._calc_reward when
+    q_next_target is None, else DDQNAgent._calc_reward.  The Q tensors may be
+    wider than 104 columns (a padded head); only the first 104 count."""
+    with torch.no_grad():
+        q = q_next_local[:, :NUM_ACTIONS]
+        if q_next_target is None:
+            best = q.max(dim=-1).values
+        else:
+            pick = torch.argmax(q, dim=-1)
+            best = q_next_target[torch.arange(q.shape[0], device=q.device), pick]
+        return reward + gamma * (best * not_done)
+
+
+# ---------------------------------------------------------------- the engine
+class BatchedDQN(BatchedPUCT):
+    def __init__(self, env, q_net, target_net=None, prioritised=False, gamma=0.99, eps_func=None, minibatch=64,
+                 updates=T_STEPS, retrain_interval=4, tau=1e-2, capacity=1 << 16, seed=0, net_dtype=torch.bfloat16,
+                 seats_mask=None, max_decisions=None):
+        """target_net given: the double-DQN target; prioritised: the PRB
+        variants (importance-weighted loss, priorities written back)"""
+        from .agents.dqn import eps_func_decay
+
+        super().__init__(env, q_net, seed=seed, seats_mask=seats_mask, puct_root=False, net_dtype=net_dtype,
+                         max_decisions=max_decisions)
+        self.target_net, self.prioritised = target_net, bool(prioritised)
+        self.gamma, self.tau = float(gamma), tau
+        self.eps_func = eps_func_decay if eps_func is None else eps_func
+        self.minibatch, self.updates, self.retrain_interval = int(minibatch), int(updates), int(retrain_interval)
+        self.capacity = int(capacity)
+        self.replay = DevicePER(self.capacity, ROW_BYTES, device=env.device)
+        # training: epsilon = eps_func(episode), episode = the rounds this engine
+        # has finished (the reference's eps_func(num_episode)); else the agent's
+        # own `eps`, which the owner sets
+        self.training, self.eps, self.episode = True, 0.0, 0
+        self.eps_used = None     # the epsilon of the latest decide
+        self.eps_history = []    # ... of every finished round
+        self.update_count = 0    # minibatch updates so far (the drop-in's `step`)
+        self.value = torch.zeros((self.D_max,), dtype=torch.float32, device=env.device)
+        self._t, self._obs, self._acts, self._flat = 0, None, None, None
+
+    # ------------------------------------------------------------ the Q net on the device
+    def sync_net(self):
+        """(re)build the device copy of the Q net in net_dtype; Linear/ReLU
+        layouts get the input weight padded to the 48-wide rows"""
+        version = tuple(p._version for p in self.actor.parameters())
+        if self._net is None or version != self._net_version:
+            net = copy.deepcopy(self.actor).to(self.env.device, self.net_dtype)
+            net.eval()
+            f = FusedMLP.of(net)
+            if f.layers is not None:
+                w, b = f.layers[0]
+                if w.shape[1] == OBS - 1:
+                    wp = torch.zeros((w.shape[0], OBS), dtype=w.dtype, device=w.device)
+                    wp[:, : OBS - 1] = w
+                    f.layers[0] = (wp, b)
+            self._net, self._net_version = f, version
+        return self._net
+
+    def _q_values(self, states):
+        """[D, >= 104] f32 with unit column stride (the padded head's view: no copy in fp32)"""
+        net = self._net
+        with torch.no_grad():
+            x = states if net.layers is not None and net.layers[0][0].shape[1] == OBS else states[:, : OBS - 1]
+            (out,) = net(x)
+        self.rows_evaluated += states.shape[0]
+        out = out.float()
+        return out if out.stride(1) == 1 else out.contiguous()
+
+    def current_eps(self):
+        return float(self.eps_func(self.episode)) if self.training else float(self.eps)
+
+    def _dec_index(self):
+        """flat g * N + p of every decision, in decision order"""
+        if self.dec is not None:
+            return self.dec.long()
+        if self._flat is None:
+            N = self.env.num_players
+            seats = torch.tensor([p for p in range(N) if (self.seats_mask >> p) & 1], device=self.env.device)
+            self._flat = (torch.arange(self.env.num_games, device=self.env.device)[:, None] * N + seats[None, :]).reshape(-1)
+        return self._flat
+
+    # ------------------------------------------------------------ acting
+    def decide(self, n, memorize=False, record=False):
+        """epsilon-greedy card of every deciding seat at hand size n: actions [B, N] int32"""
+        L, h, st = nat.lib(), self.env._h, self.env._stream()
+        self.eps_used = self.current_eps()
+        if self.D == 0:  # tournament mode: no seat of this agent in the current games
+            self.step_id += 1
+            return self.actions
+        D, dev = self.D, self.env.device
+        q = self._params(n)
+        self.sync_net()
+        obs_t = None
+        if record:
+            if self._t == 0 or self._obs.shape[1] != D:
+                self._obs = torch.zeros((T_STEPS + 1, D, OBS), dtype=torch.int8, device=dev)
+                self._acts = torch.zeros((T_STEPS, D), dtype=torch.int32, device=dev)
+                self._t = 0
+            assert self._t < T_STEPS, "end_episode() closes a recorded episode"
+            obs_t = self._obs[self._t]
+        states = torch.empty((D, OBS), dtype=self.net_dtype, device=dev)
+        nat.check(L.sn_dqn_obs(h, ctypes_ref(q), nat.ptr(obs_t), nat.ptr(states),
+                               int(self.net_dtype == torch.bfloat16), st), "sn_dqn_obs")
+        qv = self._q_values(states)
+        nat.check(L.sn_dqn_select(h, ctypes_ref(q), nat.ptr(qv), qv.stride(0), self.eps_used, nat.ptr(self.actions),
+                                  nat.ptr(self.best_index), nat.ptr(self.value), st), "sn_dqn_select")
+        if record:
+            self._acts[self._t] = self.actions.view(-1)[self._dec_index()]
+            self._t += 1
+        self.step_id += 1
+        return self.actions
+
+    def rewards_seen(self, per_step, T=None):
+        """[T, D] int32: the reward learn() gets at step t is step t-1's (0 at t = 0)"""
+        T = per_step.shape[0] if T is None else T
+        r = per_step.reshape(per_step.shape[0], -1)[: T - 1][:, self._dec_index()].to(torch.int32)
+        seen = torch.zeros((T, r.shape[1]), dtype=torch.int32, device=r.device)
+        seen[1:] = r
+        return seen
+
+    def end_episode(self, per_step):
+        """close the round: the terminal observation, the lagged rewards, the
+        packed transition rows into the replay (returned; None if nothing
+        was recorded)"""
+        rows = None
+        if self.D and self._t:
+            L, h, st = nat.lib(), self.env._h, self.env._stream()
+            T, D = self._t, self.D
+            q = self._params(0)
+            nat.check(L.sn_dqn_obs(h, ctypes_ref(q), nat.ptr(self._obs[T]), None, 0, st), "sn_dqn_obs")
+            seen = self.rewards_seen(per_step, T).contiguous()
+            rows = torch.empty((T * D, ROW_BYTES), dtype=torch.uint8, device=self.env.device)
+            nat.check(L.sn_dqn_pack(T, D, nat.ptr(self._obs), nat.ptr(self._acts), nat.ptr(seen), nat.ptr(rows), st),
+                      "sn_dqn_pack")
+            for i in range(0, T * D, self.capacity):  # ring order = sequential stores
+                self.replay.store(rows[i: i + self.capacity])
+        self._t = 0
+        self.eps_history.append(self.eps_used)
+        self.episode += 1
+        return rows
+
+    def play_episode(self, others=None, record=False):
+        """one whole game of every env game (non-deciding seats: uniform
+        moves); returns (summed rewards [B, N] int32, per-step rewards
+        [10, B, N] int32)"""
+        env = self.env
+        env.reset()
+        per_step = torch.zeros((T_STEPS, env.num_games, env.num_players), dtype=torch.int32, device=env.device)
+        keep = torch.tensor([(self.seats_mask >> p) & 1 for p in range(env.num_players)], device=env.device,
+                            dtype=torch.bool)
+        for t in range(T_STEPS):
+            acts = self.decide(T_STEPS - t, record=record)
+            if self.M < env.num_players:
+                acts = torch.where(keep[None, :], acts, self._random_moves())
+            rew, done, inv = env.step(acts)
+            per_step[t] = rew
+        self.end_episode(per_step)
+        return per_step.sum(dim=0), per_step
+
+    # ------------------------------------------------------------ learning
+    def sample_batch(self, u=None, slots=None):
+        """one minibatch of replay rows: prioritised -> DevicePER.sample (u:
+        the uniforms, drawn on the device when None); uniform -> distinct
+        slots of [0, min(len, capacity)) (History.sample's random.sample,
+        drawn on the device when `slots` is None) and DevicePER.gather"""
+        if self.prioritised:
+            idx, _, weights, rows = self.replay.sample(self.minibatch, u)
+            return {"idx": idx, "weights": weights, "rows": rows}
+        if slots is None:
+            held = min(len(self.replay), self.capacity)  # host counters: no device sync
+            slots = torch.randperm(held, device=self.env.device)[: self.minibatch].to(torch.int32)
+        return {"idx": None, "weights": None, "rows": self.replay.gather(slots)}
+
+    def unpack(self, rows):
+        n, dev = int(rows.shape[0]), self.env.device
+        s = torch.empty((n, OBS), dtype=torch.float32, device=dev)
+        s2 = torch.empty((n, OBS), dtype=torch.float32, device=dev)
+        action = torch.empty((n,), dtype=torch.int64, device=dev)
+        reward = torch.empty((n,), dtype=torch.float32, device=dev)
+        not_done = torch.empty((n,), dtype=torch.float32, device=dev)
+        nat.check(nat.lib().sn_dqn_unpack(n, nat.ptr(rows), nat.ptr(s), nat.ptr(s2), nat.ptr(action), nat.ptr(reward),
+                                          nat.ptr(not_done), self.env._stream()), "sn_dqn_unpack")
+        return s, s2, action, reward, not_done
+
+    def bellman_target(self, q_next_local, q_next_target, reward, not_done):
+        """sn_dqn_target on device tensors [n, stride >= 104] f32"""
+        assert q_next_local.stride(1) == 1 and (q_next_target is None or q_next_target.stride() == q_next_local.stride())
+        n = int(q_next_local.shape[0])
+        target = torch.empty((n,), dtype=torch.float32, device=q_next_local.device)
+        nat.check(nat.lib().sn_dqn_target(n, nat.ptr(q_next_local), nat.ptr(q_next_target), q_next_local.stride(0),
+                                          nat.ptr(reward), nat.ptr(not_done), self.gamma, nat.ptr(target),
+                                          self.env._stream()), "sn_dqn_target")
+        return target
+
+    def loss_terms(self, batch):
+        """(q_eval, target, weights, loss) of one minibatch (_learn,
+        agents/dqn.py:125-134): fp32 on the agent's own module"""
+        s, s2, action, reward, not_done = self.unpack(batch["rows"])
+        dev, here = self.actor_device(), self.env.device
+        q = self.actor(s.to(dev)[:, : OBS - 1])[0]
+        q_eval = q.gather(1, action.to(dev).view(-1, 1)).squeeze(1)
+        with torch.no_grad():
+            qn = self.actor(s2.to(dev)[:, : OBS - 1])[0].to(here).contiguous()
+            qt = None
+            if self.target_net is not None:
+                tdev = next(self.target_net.parameters()).device
+                qt = self.target_net(s2.to(tdev)[:, : OBS - 1])[0].to(here).contiguous()
+            target = self.bellman_target(qn, qt, reward, not_done).to(dev)
+        if self.prioritised:
+            weights = batch["weights"].to(dev, torch.float32)
+            loss = (weights * (q_eval - target) ** 2).mean()
+        else:
+            weights = None
+            loss = nn.functional.mse_loss(q_eval, target)
+        return q_eval, target, weights, loss
+
+    def soft_update(self, tau):
+        """theta_target = tau * theta_local + (1 - tau) * theta_target (DDQNAgent.soft_update)"""
+        for target_param, local_param in zip(self.target_net.parameters(), self.actor.parameters()):
+            target_param.data.copy_(tau * local_param.data + (1 - tau) * target_param.data)
+
+    def learn(self, optimizer):
+        """`updates` minibatch steps once the replay holds more than a
+        minibatch (the reference's gate); returns the losses (device scalars)"""
+        if len(self.replay) <= self.minibatch:
+            return []
+        losses = []
+        for _ in range(self.updates):
+            batch = self.sample_batch()
+            q_eval, target, weights, loss = self.loss_terms(batch)
+            if self.prioritised:  # DQN_PRBAgent._update_memory, before the optimiser step
+                self.replay.update(batch["idx"], torch.abs(q_eval.detach() - target))
+            self.update_count += 1
+            if self.target_net is not None and self.update_count % self.retrain_interval == 0:
+                self.soft_update(self.tau)
+            optimizer.zero_grad()
+            loss.backward()
+            optimizer.step()
+            losses.append(loss.detach())
+        return losses

@@ -31,7 +31,14 @@ Agents (the pool of run.py:20-40):
     Their random draws are Philox, not torch's CPU generator (parity
     unpinned, like the engines themselves), and they consume no numpy words
     (the reference's _draw_env shuffles do), so a league with net agents is
-    the reference's in law, not draw for draw.
+    the reference's in law, not draw for draw;
+  * DQNVanilla / DDQNAgent / DQN_PRBAgent / DDQN_PRBAgent -- dqn.BatchedDQN
+    (`engine_kind` -> "dqn"; `agent_kind`, the map of the AGENTS registry,
+    still has no answer for them): raw observation rows, the Q net on
+    PyTorch-ROCm, an epsilon-greedy Philox selection; with train=True the
+    round's transitions go into the engine's DevicePER ring and the agent
+    takes T_STEPS minibatch updates of max(agent.minibatch, slots) rows per
+    round.  A clone's engine starts with an empty replay.
 All-DrunkHamster leagues play whole games per launch (sn_league_rollout,
 `fused`); every other league plays sn_reset (seat draw + deal) then 10
 sn_league_step launches per game round.
@@ -57,7 +64,8 @@ logger = logging.getLogger(__name__)
 STAT_GAMES, STAT_SCORE, STAT_POSITION, STAT_WINS = range(4)
 KIND_RANDOM, KIND_MCS, KIND_PUCT, KIND_CUSTOMED, KIND_ACER = "random", "mcs", "puct", "customed", "acer"
 KIND_REINFORCE = "reinforce"
-NET_KINDS = (KIND_PUCT, KIND_CUSTOMED, KIND_ACER, KIND_REINFORCE)
+KIND_DQN = "dqn"
+NET_KINDS = (KIND_PUCT, KIND_CUSTOMED, KIND_ACER, KIND_REINFORCE, KIND_DQN)
 T_STEPS = 10
 
 
@@ -78,6 +86,16 @@ def agent_kind(agent):
     if isinstance(agent, DrunkHamster):
         return KIND_RANDOM
     raise NotImplementedError(f"the batched tournament has no engine for {type(agent).__name__}")
+
+
+def engine_kind(agent):
+    """the batched engine that seats `agent` in a BatchedTournament: KIND_DQN
+    for the four DQN drop-ins (dqn.BatchedDQN), else agent_kind's answer"""
+    from .agents.dqn import DQNVanilla
+
+    if isinstance(agent, DQNVanilla):  # DDQNAgent, DQN_PRBAgent and DDQN_PRBAgent derive from it
+        return KIND_DQN
+    return agent_kind(agent)
 
 
 def decode_seats(words, max_players):
@@ -196,7 +214,7 @@ class BatchedTournament:
             raise NotImplementedError("the fused all-DrunkHamster league has drawn its next seats already; add every "
                                       "player before the first game (or use fused=False)")
         agent = DrunkHamster() if agent is None else agent
-        kind = agent_kind(agent)
+        kind = engine_kind(agent)
         agent.__name__ = name  # tournament.py:40
         self.names.append(name)
         self.agents[name], self.kinds[name] = agent, kind
@@ -369,6 +387,7 @@ class BatchedTournament:
     def _engine(self, name):
         """the batched engine of one net agent over this handle (decision-list mode)"""
         from .acer import BatchedACER
+        from .dqn import BatchedDQN
         from .puct import BatchedPUCT, BatchedPUCTCustomed
         from .reinforce import BatchedReinforce
 
@@ -389,11 +408,24 @@ class BatchedTournament:
             return BatchedReinforce(env, agent.actor, net_dtype=self.net_dtype, seed=seed, gamma=agent.gamma,
                                     r_factor=agent.r_factor, actor_weight=agent.actor_weight,
                                     entropy_weight=agent.entropy_weight, max_decisions=B)
+        K = max(1, len(self.active_agents()))
+        seats = B * (self.min_players + self.max_players) / 2.0 / K  # expected seats of this agent per round
+        if kind == KIND_DQN:
+            # T_STEPS minibatch updates per round (the reference's learn calls per game), each on at least
+            # one row per slot; a ring of two expected rounds of transitions at least (a power of two).
+            # agent.history, the drop-in's host buffer, stays unused (copy_player's deepcopy keeps working).
+            from .agents.dqn import DQN_PRBAgent
+
+            need = max(int(agent.history.max_length or 0), int(2 * T_STEPS * seats), 2)
+            capacity = 1 << (need - 1).bit_length()
+            return BatchedDQN(env, agent.dqn_net_local, target_net=getattr(agent, "dqn_net_target", None),
+                              prioritised=isinstance(agent, DQN_PRBAgent), gamma=agent.gamma, eps_func=agent.eps_func,
+                              minibatch=max(int(agent.minibatch), B), updates=T_STEPS,
+                              retrain_interval=getattr(agent, "retrain_interval", 4), tau=getattr(agent, "tau", 1e-2),
+                              capacity=capacity, seed=seed, net_dtype=self.net_dtype, max_decisions=B)
         # replay rounds: enough that the stored sequences (every seat of the
         # agent in each kept round, ceil(10 / rollout_len) per seat) pass
         # max(warmup, minibatch), from the expected seats per round
-        K = max(1, len(self.active_agents()))
-        seats = B * (self.min_players + self.max_players) / 2.0 / K
         chunks = -(-T_STEPS // int(agent.rollout_len))
         need = max(int(agent.warmup), int(agent.batchsize)) + 1
         capacity = max(2, int(-(-need // max(1.0, seats * chunks))) + 1)
@@ -470,12 +502,17 @@ class BatchedTournament:
     def _round(self):
         """one game per slot: sn_reset (seat draw + deal), then 10 x [net
         agents' engines on their seats -> sn_league_step]"""
+        from .dqn import BatchedDQN
+
         env, L, st = self.env, nat.lib(), self.env._stream()
         B, N, dev = self.num_slots, self.max_players, env.device
         self._phase_events = []
         with self._phase("reset (seat draw + deal) + decision lists"):
             nat.check(L.sn_reset(env._h, None, st), "sn_reset")  # Tournament.play_game: seats, then the deal
             self._use_decisions()
+        dqn = {n: e for n, e in self.engines.items() if isinstance(e, BatchedDQN)}
+        for name, eng in dqn.items():  # training: eps_func(rounds finished); else the agent's own eps
+            eng.training, eng.eps = self.train, self.agents[name].eps
         acts = torch.zeros((B, N), dtype=torch.int32, device=dev)
         per_step = torch.zeros((T_STEPS, B, N), dtype=torch.int32, device=dev)
         rec = torch.zeros((B, 1 + N), dtype=torch.int32, device=dev)
@@ -495,6 +532,9 @@ class BatchedTournament:
                 nat.check(L.sn_league_step(env._h, nat.ptr(acts), nat.ptr(per_step[t]), None,
                                            nat.ptr(rec) if t == T_STEPS - 1 else None, nat.ptr(invalid[t]),
                                            nat.ptr(status), st), "sn_league_step")
+        for name, eng in dqn.items():
+            with self._phase(f"store {name}"):
+                eng.end_episode(per_step)  # terminal observation, lagged rewards, rows into the replay
         if self.engines:  # external seats played: an illegal card fails the round (sechs.h) -- checked once
             # per round, not per step: a host read-back per step kept the host from enqueueing the next
             # step's searches while the GPU ran this one
@@ -523,6 +563,7 @@ class BatchedTournament:
     def _learn(self, per_step):
         """one Adam step per net agent on its loss over the round's games"""
         from .acer import BatchedACER
+        from .dqn import BatchedDQN
         from .puct import BatchedPUCTCustomed
         from .reinforce import BatchedReinforce
 
@@ -535,6 +576,11 @@ class BatchedTournament:
                     if eng.D:
                         eng.record_rewards(per_step)
                         eng.learn(agent.optimizer)
+                    continue
+                if isinstance(eng, BatchedDQN):  # its own schedule too: `updates` minibatches per round
+                    if eng.D:
+                        steps = len(eng.learn(agent.optimizer))
+                        self.optimizer_steps[name] = self.optimizer_steps.get(name, 0) + steps
                     continue
                 if eng.D == 0 or not eng.decisions:
                     continue

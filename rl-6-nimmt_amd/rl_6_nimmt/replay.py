@@ -5,7 +5,9 @@ sn_per_* entry points of include/sechs.h).
 `DevicePER(capacity, row_bytes)` holds the f64 sum tree in the reference's
 heap layout and, with `row_bytes` > 0, a ring of fixed-size payload rows
 (observations, action, reward, done packed by the caller) that `sample`
-gathers on the device -- what a batched league DQN learner stands on.  The
+gathers on the device and `gather` returns for given slots: the batched
+league DQN learner (dqn.BatchedDQN) stores its 112-byte transition rows
+there, the prioritised variants sampling, the uniform ones gathering.  The
 drop-in `PriorityReplayBuffer` (utils/replay_buffer.py) uses it with
 `row_bytes=0` and keeps its experience dicts on the host.
 
@@ -127,6 +129,25 @@ class DevicePER:
         nat.check(nat.lib().sn_per_sample(h, n, nat.ptr(u), float(self.beta), nat.ptr(idx), nat.ptr(prio),
                                           nat.ptr(weight), nat.ptr(rows), self._stream()), "sn_per_sample")
         return idx, prio, weight, rows
+
+    def gather(self, slots):
+        """-> the payload rows uint8 [n][row_bytes] of the data slots `slots`
+        (int32 [n] on the device; slot = tree index - capacity + 1); a slot
+        outside [0, capacity) gives a zero row.  The uniform replay of
+        DQNVanilla / DDQNAgent: the caller draws the slots."""
+        h = self._handle()
+        if self.row_bytes == 0:
+            raise ValueError("this replay holds no payload rows (row_bytes=0)")
+        slots = torch.as_tensor(slots).to(self.device).reshape(-1)
+        if slots.dtype != torch.int32:
+            slots = slots.to(torch.int64).clamp(-1, 2**31 - 1).to(torch.int32)
+        slots = slots.contiguous()
+        n = int(slots.numel())
+        if n < 1:
+            raise ValueError("n must be >= 1")
+        rows = torch.empty((n, self.row_bytes), dtype=torch.uint8, device=self.device)
+        nat.check(nat.lib().sn_per_gather(h, n, nat.ptr(slots), nat.ptr(rows), self._stream()), "sn_per_gather")
+        return rows
 
     def update(self, tree_idx, abs_err, epsilon=None, upper=None, alpha=None):
         """Leaf tree_idx[i] = min(abs_err[i] + epsilon, upper) ** alpha; of a
