@@ -208,6 +208,17 @@ sn_status sn_philox_counter(sn_env* env, int64_t game, uint64_t* counter_host);
                          words, same outputs, same exported numpy states;
                          the environment variable SECHS_TWIST_DEPTH
                          overrides the default at sn_create.
+     SN_OPT_PLAY_GROUP   1 (default): a decode-ahead rollout of more than one
+                         chunk (SN_OPT_CHUNK_STEPS) plays its consecutive
+                         chunks of one twist group (SN_OPT_TWIST_EVERY = K, so
+                         up to K chunks, never across a group boundary) in one
+                         k_play launch, which moves from episode record to
+                         episode record at every deal; the twists, decodes and
+                         the waits between groups stay where they are.  0: one
+                         launch per chunk.  Tournament handles and the
+                         ring-reading paths keep one launch per chunk (their
+                         launches are bounded by the ring window).  Same
+                         outputs, same exported numpy states.
    A pipelined (numpy-compat) rollout records its ordering event on the
    caller's stream before it returns; every later call waits on that event
    (also on the same stream), so the caller may destroy the stream after
@@ -215,7 +226,7 @@ sn_status sn_philox_counter(sn_env* env, int64_t game, uint64_t* counter_host);
 enum { SN_OPT_RING_WORDS = 1, SN_OPT_CHUNK_STEPS = 2, SN_OPT_PIPELINE = 3, SN_OPT_TIMING = 4, SN_OPT_PIPE_GPW = 5,
        SN_OPT_PIPE_LEAD = 6, SN_OPT_PLAY_SPLIT = 7, SN_OPT_PLAY_QUAD = 8, SN_OPT_TWIST_ROUND = 9,
        SN_OPT_TWIST_EVERY = 10, SN_OPT_PIPE_FUSED = 11, SN_OPT_TWIST_SKIP = 12, SN_OPT_PIPE_DEC = 13,
-       SN_OPT_TWIST_DEPTH = 14 };
+       SN_OPT_TWIST_DEPTH = 14, SN_OPT_PLAY_GROUP = 15 };
 sn_status sn_set_option(sn_env* env, int option, int value);
 /* pipelined rollouts whose draws ran past the twisted words (must be 0; a
    nonzero count means those games' draws are wrong) [sync].  The count is

@@ -671,7 +671,7 @@ struct PlayArgs {
     int step0;               // league: env-steps of this rollout before this launch (episode index of a record)
     int n0;                  // k_play_split: every game's hand size at the launch's start (aligned handle);
                              // RNG_NUMPY_DEC: the launch's first step within its episode (0..9)
-    int drec0, drec1;        // RNG_NUMPY_DEC: record slots of the launch's episode and of the next one
+    int drec0;               // RNG_NUMPY_DEC: record slot of the launch's first episode (the next ones follow, mod kDecRecords)
 };
 
 // The env-step loop of one lane (game g).  R supplies the random words
@@ -746,46 +746,40 @@ __device__ __forceinline__ uint32_t dec_u16(const uint32_t (&w)[kDecWords], int 
 
 template <int N>
 struct DecSrc {
-    uint32_t A[kDecWords];  // the launch's episode
-    uint32_t B1[11];        // the next episode: w0..w10 (its draws, offsets), when the launch crosses into it
-    int phi;                // the launch's first step within its episode
+    uint32_t A[kDecWords];  // the current episode's record
+    const u32x4* rec;       // drec + g: this game's piece 0 of record slot 0
+    int64_t B;
+    int slot;               // record slot of the current episode
+    int base;               // the launch step that is the current episode's step 0 (at load: minus the launch's first step
+                            // within its episode, -9 .. 0)
+    int end;                // the launch's steps
 
-    __device__ __forceinline__ void load(const DevState& s, const PlayArgs& a, int64_t g, bool cross) {
-        phi = a.n0;
-        const u32x4* ra = s.drec + (int64_t)a.drec0 * kDecQuads * s.B + g;
+    __device__ __forceinline__ void fetch() {
+        const u32x4* ra = rec + (int64_t)slot * kDecQuads * B;
 #pragma unroll
         for (int q = 0; q < kDecQuads; q++) {
-            const u32x4 v = ra[(int64_t)q * s.B];
+            const u32x4 v = ra[(int64_t)q * B];
             A[4 * q] = v.x, A[4 * q + 1] = v.y, A[4 * q + 2] = v.z, A[4 * q + 3] = v.w;
         }
-#pragma unroll
-        for (int k = 0; k < 11; k++) B1[k] = 0u;
-        if (cross) {
-            const u32x4* rb = s.drec + (int64_t)a.drec1 * kDecQuads * s.B + g;
-#pragma unroll
-            for (int q = 0; q < 3; q++) {
-                const u32x4 v = rb[(int64_t)q * s.B];
-                B1[4 * q] = v.x, B1[4 * q + 1] = v.y, B1[4 * q + 2] = v.z;
-                if (q < 2) B1[4 * q + 3] = v.w;
-            }
-        }
+    }
+    __device__ __forceinline__ void load(const DevState& s, const PlayArgs& a, int64_t g) {
+        rec = s.drec + g, B = s.B;
+        slot = a.drec0, base = -a.n0, end = a.steps;
+        fetch();
     }
     __device__ __forceinline__ void draws(const Game<N>&, int t, uint32_t, bool, uint32_t (&idx)[N]) {
-        const int tau = phi + t;  // wave-uniform
-        uint32_t v;
-        if (tau < kHand) {
-            v = (tau < kHand - 1) ? dec_u16(A, 6, tau) : 0u;
-        } else {
-            uint32_t w[kDecWords];
-#pragma unroll
-            for (int k = 0; k < kDecWords; k++) w[k] = (k < 11) ? B1[k] : 0u;
-            v = (tau - kHand < kHand - 1) ? dec_u16(w, 6, tau - kHand) : 0u;
-        }
+        const int tau = t - base;  // wave-uniform: the step within the episode
+        SN_DASSERT(tau >= 0 && tau < kHand);
+        const uint32_t v = (tau < kHand - 1) ? dec_u16(A, 6, tau) : 0u;
 #pragma unroll
         for (int p = 0; p < N; p++) idx[p] = (v >> (4 * p)) & 15u;
     }
     __device__ __forceinline__ uint32_t league(const DevState&) { return 0u; }
-    __device__ __forceinline__ void deal(const DevState&, Game<N>& G, PhaseProf&) {  // the next episode's deal
+    // The next episode's deal, then -- a launch that plays on (up to a whole twist group of
+    // launches, K deals) -- the next episode's record: the one place where the step loop
+    // loads, once per episode, waited for here behind this step's few small stores and not
+    // at the first draw behind the next step's observation stores (vmcnt counts in order).
+    __device__ __forceinline__ void deal(const DevState&, Game<N>& G, PhaseProf&) {
 #pragma unroll
         for (int p = 0; p < N; p++) {
             G.hand[p].lo = (uint64_t)A[12 + 3 * p] | ((uint64_t)A[13 + 3 * p] << 32);
@@ -797,15 +791,19 @@ struct DecSrc {
         G.b.lo = u32x4{r0, r1, r2, r3};
         G.b.hi = u32x4{meta_row(r0), meta_row(r1), meta_row(r2), meta_row(r3)};
         G.n = kHand;
+        if (base + kHand < end) {  // wave-uniform (lockstep games)
+            base += kHand;
+            slot = (slot + 1 == kDecRecords) ? 0 : slot + 1;
+            fetch();
+#pragma unroll
+            for (int k = 0; k < kDecWords; k++) asm volatile("" : "+v"(A[k]));
+        }
     }
     // the stream position after the launch's last step (what sn_pipe_sync exports)
-    __device__ __forceinline__ uint32_t position(int steps) const {
-        const int last = phi + steps - 1;
-        if (last < kHand) return A[0] + dec_u16(A, 1, last);
-        uint32_t w[kDecWords];
-#pragma unroll
-        for (int k = 0; k < kDecWords; k++) w[k] = (k < 11) ? B1[k] : 0u;
-        return w[0] + dec_u16(w, 1, last - kHand);
+    __device__ __forceinline__ uint32_t position() const {
+        const int last = end - 1 - base;  // 0 .. 9: a launch that ends on a deal keeps that episode's record
+        SN_DASSERT(last >= 0 && last < kHand);
+        return A[0] + dec_u16(A, 1, last);
     }
 };
 
@@ -1009,10 +1007,10 @@ __device__ __forceinline__ void play_body(const DevState& s, const PlayArgs& a, 
     ByteBuf buf;
     if constexpr (MODE == RNG_NUMPY_DEC) {
         DecSrc<N> src;
-        src.load(s, a, g, a.n0 + a.steps > kHand);
+        src.load(s, a, g);
         pp.mark(PH_PROLOGUE);
         play_steps<N, DecSrc<N>, 64, false>(s, a, g, lane, wave_lds, G, src, sum_res, episodes, pp, lg, 0, a.steps);
-        s.pabsc[(int64_t)a.pipe_cout * s.B + g] = src.position(a.steps);  // the consumer position (sn_pipe_sync)
+        s.pabsc[(int64_t)a.pipe_cout * s.B + g] = src.position();  // the consumer position (sn_pipe_sync)
     } else if constexpr (MODE == RNG_NUMPY_PIPE) {
         RingPipe rng;
         rng.load(s, g, buf, wave_lds + a.wave_lds - GPW * a.ring_lds + lane * a.ring_lds, a.pipe_cin, a.pipe_t);
@@ -1042,8 +1040,14 @@ __device__ __forceinline__ void play_body(const DevState& s, const PlayArgs& a, 
     pp.flush(lane);
 }
 
+// Decode-ahead at N = 4 (251 VGPRs; 259 before the launch could span a twist group): at most
+// one wave per SIMD as ever -- the allocation is padded past half the file -- so that no CU
+// takes two of the launch's 53-KB blocks (one per CU at 65 536 games) while another holds none:
+// without the bound the 10-step launch measured 12 % slower.
 template <int N, int MODE, int GPW = 64, bool LG = false>
-__global__ __launch_bounds__(kBlock) void k_play(DevState s, PlayArgs a) {
+__global__ __launch_bounds__(kBlock)
+__attribute__((amdgpu_waves_per_eu(1, (MODE == RNG_NUMPY_DEC && N == kSplitMaxPlayers) ? 1 : 8)))
+void k_play(DevState s, PlayArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds_dyn[];
     play_body<N, MODE, GPW, LG>(s, a, lds_dyn, (int)threadIdx.x);
 }
@@ -1761,6 +1765,11 @@ sn_status sn_create(sn_env** out, int device, int64_t num_games, int num_players
         const char* ps = getenv("SECHS_PIPE_SERIAL");
         e->opt.pipe_serial = (ps && ps[0] == '1') ? 1 : 0;
     }
+    e->opt.play_group = 1;  // one k_play launch per twist group where a call spans it
+    {
+        const char* pg = getenv("SECHS_PLAY_GROUP");  // default override (A/B runs of whole legs)
+        if (pg && (pg[0] == '0' || pg[0] == '1') && !pg[1]) e->opt.play_group = pg[0] - '0';
+    }
     e->opt.pipe_dec = 1;  // decode-ahead where it applies: 0.0776 -> 0.069 ms per step same box
     {
         const char* pd = getenv("SECHS_PIPE_DEC");  // default override (A/B runs of whole legs)
@@ -1918,6 +1927,10 @@ sn_status sn_set_option(sn_env* e, int option, int value) {
         case SN_OPT_PIPE_DEC:
             if (value < 0 || value > 1) return fail(SN_EINVAL, "pipe dec must be 0 or 1");
             e->opt.pipe_dec = value;
+            return SN_OK;
+        case SN_OPT_PLAY_GROUP:  // the launch form only: the pipeline's bookkeeping is in chunks either way, no restart
+            if (value < 0 || value > 1) return fail(SN_EINVAL, "play group must be 0 or 1");
+            e->opt.play_group = value;
             return SN_OK;
         case SN_OPT_TWIST_SKIP:
             if (value < 0 || value > 1) return fail(SN_EINVAL, "twist skip must be 0 or 1");
@@ -2234,7 +2247,11 @@ static sn_status pipe_twist(sn_env* e, uint64_t G, uint64_t p, int64_t e_start, 
         // its launches start at most K episodes past this launch's and touch at most one
         // more each: episodes < e_start + 2K + 1 (the ring of kDecRecords >= 2K + 2
         // slots never overwrites one a running launch reads: the oldest, launch p-K,
-        // reads episodes >= e_start - K, 3K + 1 <= kDecRecords).  It reads the words twist
+        // reads episodes >= e_start - K, 3K + 1 <= kDecRecords).  A fused launch
+        // (SN_OPT_PLAY_GROUP) covers chunks of one group only and loads, deal by deal, the
+        // records its chunks would have loaded as launches of their own: the same episodes
+        // (>= e_start - K for the group before), while it runs in those launches' place on
+        // the play stream, so the bound holds unchanged.  It reads the words twist
         // G-1 twisted and waits for that twist only (which waited for launch p-K-1), and
         // its position goes to the decoder slot of decode G, which twist G+1 reads.
         const int64_t target = e_start + 2 * pl.K + 1;
@@ -2283,7 +2300,9 @@ static sn_status pipe_twist(sn_env* e, uint64_t G, uint64_t p, int64_t e_start, 
 // so it leads the decoder position after decode G-1 by the words of the
 // 2K + 1 episodes decode G+1 may need: 600 (K + 1) words (~200 per episode at
 // N <= 4), and the play launches (one launch plan: no deck, no ring window)
-// read no ring at all.  Otherwise the twists lead the play consumer by 600 K words.
+// read no ring at all -- so the 10-step limit does not bind them, and one launch plays
+// the call's chunks of a whole group (SN_OPT_PLAY_GROUP, the loop below).  Otherwise the
+// twists lead the play consumer by 600 K words.
 static sn_status launch_pipe(sn_env* e, PlayArgs a, LdsPlan plan, hipStream_t st) {
     const DevState& s = e->s;
     sn_env::Pipeline& pl = e->pl;
@@ -2310,15 +2329,21 @@ static sn_status launch_pipe(sn_env* e, PlayArgs a, LdsPlan plan, hipStream_t st
     // (tools/pipe_tail.py), beyond that 5-step launches
     const int chunk = min(e->opt.chunk_steps, (s.lg_K > 8) ? 5 : pipe_max_chunk(s.N));
     int phase = dec ? e->phase : 0;  // decode-ahead: the games' step within their episode
-    for (int t0 = 0; t0 < a.steps; t0 += chunk) {
-        PlayArgs c = slice_steps(a, t0, min(chunk, a.steps - t0), s.B, s.N);
+    // SN_OPT_PLAY_GROUP, decode-ahead only: one k_play launch for the call's consecutive chunks
+    // of one twist group -- the tail bound above limits whoever reads the ring, here k_decode;
+    // k_play reads records finished a group earlier.  The bookkeeping stays in chunks.
+    const bool fuse = dec && e->opt.play_group;
+    for (int t0 = 0, m = 1; t0 < a.steps; t0 += m * chunk) {
         const uint64_t p = pl.launches, G = p / (uint64_t)K;
         const bool first = (p % (uint64_t)K) == 0u;  // twist G beside this launch
-        c.pipe_cin = pabsc_in(p), c.pipe_cout = pabsc_out(p);
+        // chunks [p, p + m) in this launch: to the end of the call or of group G, whichever is first
+        m = fuse ? (int)min((int64_t)(a.steps - t0 + chunk - 1) / chunk, (int64_t)K - (int64_t)(p % (uint64_t)K)) : 1;
+        PlayArgs c = slice_steps(a, t0, min(m * chunk, a.steps - t0), s.B, s.N);
+        c.pipe_cin = pabsc_in(p), c.pipe_cout = pabsc_out(p + (uint64_t)m - 1u);
         c.pipe_t = ptend_slot(G - 1);  // twist G-1's end (the start-up's for group 0)
-        if (dec) {  // the launch's records: its episode's and (crossing a deal) the next one's
+        if (dec) {  // the launch's records: its first episode's, then (past each deal) the next one's
             c.n0 = phase;
-            c.drec0 = dec_record(pl.dec_e), c.drec1 = dec_record(pl.dec_e + 1);
+            c.drec0 = dec_record(pl.dec_e);
         }
         // twist G-1 (decode-ahead: decode G-1, which waited for twist G-1 itself)
         if (first && G >= 1u) HIP_TRY(hipStreamWaitEvent(st, (dec ? pl.evd : pl.evt)[ptend_slot(G - 1)], 0));
@@ -2330,15 +2355,15 @@ static sn_status launch_pipe(sn_env* e, PlayArgs a, LdsPlan plan, hipStream_t st
         if (const sn_status r = launch_play_mode(s, c, mode, gpw, st); r != SN_OK) return r;  // decode-ahead: gpw == 64
         const int64_t e_start = pl.dec_e;  // the episode this launch started in
         if (dec) {
-            phase += c.steps;
-            if (phase >= kHand) phase -= kHand, pl.dec_e++;
+            phase += c.steps;  // as if the chunks had been launched one by one
+            pl.dec_e += phase / kHand, phase %= kHand;
         }
         if (tv) HIP_TRY(hipEventRecord(tv[1], st));
         if (first) {
             if (const sn_status r = pipe_twist(e, G, p, e_start, lead, ti, st); r != SN_OK) return r;
         }
         pl.pl_cout = c.pipe_cout;
-        pl.launches++;
+        pl.launches += (uint64_t)m;
     }
     // behind this rollout's last k_play, on the caller's stream of THIS call:
     // the next call (or sn_pipe_sync) orders behind it without touching a
