@@ -55,6 +55,15 @@ def default_capacity(rollout_len=10, minibatch=5, warmup=100):
     return max(4, -(-need // chunks) + 1)
 
 
+def league_capacity(warmup, minibatch, rollout_len, seats):
+    """replay rounds of a league engine: enough that the stored sequences
+    (every seat of the agent in each kept round -- `seats` expected per
+    round -- ceil(10 / rollout_len) per seat) pass max(warmup, minibatch)"""
+    chunks = -(-T_STEPS // int(rollout_len))
+    need = max(int(warmup), int(minibatch)) + 1
+    return max(2, int(-(-need // max(1.0, seats * chunks))) + 1)
+
+
 def replay_bytes(capacity, decisions):
     """device bytes of a replay of `capacity` episodes x 10 steps x
     `decisions` deciders: fp32 candidate rows [10][48], chosen slot (int64),
@@ -152,7 +161,6 @@ class BatchedACER(BatchedPUCT):
         if self.D == 0:
             self.step_id += 1
             return self.actions
-        bf16 = int(self.net_dtype == torch.bfloat16)
         q = self._params(n)
         # recording with the actor on this device: the training-precision
         # forward (fp32 rows) is the one sampled from, so the behaviour log pi
@@ -166,8 +174,7 @@ class BatchedACER(BatchedPUCT):
             self.rows_evaluated += r32.shape[0]
         else:
             self.sync_net()
-            rows = torch.empty((self.D * n, ROW), dtype=self.net_dtype, device=self.env.device)
-            nat.check(L.sn_puct_root_rows(h, ctypes_ref(q), nat.ptr(rows), bf16, st), "sn_puct_root_rows")
+            rows = self._root_rows(q, n)
             with torch.no_grad():
                 logit, _ = self._net(rows)
             self.rows_evaluated += rows.shape[0]
@@ -199,33 +206,17 @@ class BatchedACER(BatchedPUCT):
         """one whole game of every env game (non-deciding seats: uniform moves);
         with record, the episode goes into replay slot episodes % capacity.
         Returns (summed rewards [B, N] int32, per-step rewards [10, B, N])."""
-        env = self.env
-        env.reset()
-        per_step = torch.zeros((T_STEPS, env.num_games, env.num_players), dtype=torch.int32, device=env.device)
-        for t in range(T_STEPS):
-            acts = self.decide(T_STEPS - t, record=record)
-            if self.M < env.num_players:
-                keep = torch.tensor([(self.seats_mask >> p) & 1 for p in range(env.num_players)], device=env.device,
-                                    dtype=torch.bool)
-                acts = torch.where(keep[None, :], acts, self._random_moves())
-            rew, done, inv = env.step(acts)
-            per_step[t] = rew
+        self.episode_rewards = per_step = self._play_steps(record)
         if record:
-            seats = [p for p in range(env.num_players) if (self.seats_mask >> p) & 1]
-            # learn(next_reward=r_t) of the step's own reward, x r_factor in float64 (actor_critic.py:142)
-            r = per_step[:, :, seats].reshape(T_STEPS, -1).double() * self.r_factor
-            self.rep_rew[self.episodes % self.capacity] = r.float()
-            self.rep_nd[self.episodes % self.capacity] = self.D
-            self.episodes += 1
-        self.episode_rewards = per_step
+            self.record_rewards(per_step)
         return per_step.sum(dim=0), per_step
 
     def record_rewards(self, per_step):
-        """tournament mode: close the round's episode -- the rewards of this
-        agent's seats (per_step [10, B, N] int32, learn(next_reward=r_t) of
-        the step's own reward x r_factor, actor_critic.py:142)"""
+        """close the recorded episode -- the rewards of the deciding seats
+        (per_step [10, B, N] int32, learn(next_reward=r_t) of the step's own
+        reward x r_factor in float64, actor_critic.py:142)"""
         s = self.episodes % self.capacity
-        r = per_step.reshape(T_STEPS, -1)[:, self.dec.long()].double() * self.r_factor
+        r = self.decider_rewards(per_step).double() * self.r_factor
         self.rep_rew[s, :, : self.D] = r.float()
         self.rep_nd[s] = self.D
         self.episodes += 1
@@ -409,3 +400,36 @@ class BatchedACER(BatchedPUCT):
         done_updates = [tuple(float(v) for v in u) for u in torch.stack(done_updates).cpu()] if done_updates else []
         self.last_losses += done_updates
         return done_updates
+
+    # ------------------------------------------------------------ the league's protocol (puct.BatchedPUCT)
+    @classmethod
+    def from_agent(cls, env, agent, *, seed, net_dtype, slots, seats):
+        return cls(env, agent.actor_critic, net_dtype=net_dtype, seed=seed, gamma=agent.gamma,
+                   rollout_len=agent.rollout_len, minibatch=agent.batchsize, truncate=agent.truncate,
+                   warmup=agent.warmup, r_factor=agent.r_factor, critic_weight=agent.critic_weight,
+                   capacity=league_capacity(agent.warmup, agent.batchsize, agent.rollout_len, seats),
+                   log_epsilon=agent.log_epsilon, max_decisions=slots)
+
+    def learn_round(self, optimizer, per_step, updates_per_round):
+        """ACER keeps its own update schedule (learn); the league does not count its steps"""
+        if self.D:
+            self.record_rewards(per_step)
+            self.learn(optimizer)
+
+    def inherit(self, parent):
+        """a clone's engine starts from its parent's replay, as the
+        reference's copy_player carries the agent's history through its
+        torch.save round trip (tournament.py:54-60, the agent's
+        SequentialHistory): the parent's most recent episodes, oldest first,
+        up to this engine's capacity"""
+        if not isinstance(parent, BatchedACER) or self.rep_rows.shape[1:] != parent.rep_rows.shape[1:]:
+            return
+        n = min(parent.episodes, parent.capacity, self.capacity)
+        with torch.no_grad():
+            for k in range(n):
+                a, b = (parent.episodes - n + k) % parent.capacity, k % self.capacity
+                for dst, src in ((self.rep_rows, parent.rep_rows), (self.rep_act, parent.rep_act),
+                                 (self.rep_logp, parent.rep_logp), (self.rep_rew, parent.rep_rew)):
+                    dst[b].copy_(src[a])
+                self.rep_nd[b] = parent.rep_nd[a]
+        self.episodes = n

@@ -95,6 +95,13 @@ def bellman_target_host(q_next_local, q_next_target, reward, not_done, gamma):
         return reward + gamma * (best * not_done)
 
 
+def league_capacity(history_length, seats):
+    """replay rows of a league engine: the drop-in's history length and at least two expected rounds of
+    transitions (`seats` expected seats of the agent per round, T_STEPS rows each), as a power of two"""
+    need = max(int(history_length or 0), int(2 * T_STEPS * seats), 2)
+    return 1 << (need - 1).bit_length()
+
+
 # ---------------------------------------------------------------- the engine
 class BatchedDQN(BatchedPUCT):
     def __init__(self, env, q_net, target_net=None, prioritised=False, gamma=0.99, eps_func=None, minibatch=64,
@@ -120,7 +127,7 @@ class BatchedDQN(BatchedPUCT):
         self.eps_history = []    # ... of every finished round
         self.update_count = 0    # minibatch updates so far (the drop-in's `step`)
         self.value = torch.zeros((self.D_max,), dtype=torch.float32, device=env.device)
-        self._t, self._obs, self._acts, self._flat = 0, None, None, None
+        self._t, self._obs, self._acts = 0, None, None
 
     # ------------------------------------------------------------ the Q net on the device
     def sync_net(self):
@@ -153,16 +160,6 @@ class BatchedDQN(BatchedPUCT):
     def current_eps(self):
         return float(self.eps_func(self.episode)) if self.training else float(self.eps)
 
-    def _dec_index(self):
-        """flat g * N + p of every decision, in decision order"""
-        if self.dec is not None:
-            return self.dec.long()
-        if self._flat is None:
-            N = self.env.num_players
-            seats = torch.tensor([p for p in range(N) if (self.seats_mask >> p) & 1], device=self.env.device)
-            self._flat = (torch.arange(self.env.num_games, device=self.env.device)[:, None] * N + seats[None, :]).reshape(-1)
-        return self._flat
-
     # ------------------------------------------------------------ acting
     def decide(self, n, memorize=False, record=False):
         """epsilon-greedy card of every deciding seat at hand size n: actions [B, N] int32"""
@@ -189,7 +186,7 @@ class BatchedDQN(BatchedPUCT):
         nat.check(L.sn_dqn_select(h, ctypes_ref(q), nat.ptr(qv), qv.stride(0), self.eps_used, nat.ptr(self.actions),
                                   nat.ptr(self.best_index), nat.ptr(self.value), st), "sn_dqn_select")
         if record:
-            self._acts[self._t] = self.actions.view(-1)[self._dec_index()]
+            self._acts[self._t] = self.actions.view(-1)[self.decider_index()]
             self._t += 1
         self.step_id += 1
         return self.actions
@@ -197,7 +194,7 @@ class BatchedDQN(BatchedPUCT):
     def rewards_seen(self, per_step, T=None):
         """[T, D] int32: the reward learn() gets at step t is step t-1's (0 at t = 0)"""
         T = per_step.shape[0] if T is None else T
-        r = per_step.reshape(per_step.shape[0], -1)[: T - 1][:, self._dec_index()].to(torch.int32)
+        r = self.decider_rewards(per_step)[: T - 1].to(torch.int32)
         seen = torch.zeros((T, r.shape[1]), dtype=torch.int32, device=r.device)
         seen[1:] = r
         return seen
@@ -227,17 +224,7 @@ class BatchedDQN(BatchedPUCT):
         """one whole game of every env game (non-deciding seats: uniform
         moves); returns (summed rewards [B, N] int32, per-step rewards
         [10, B, N] int32)"""
-        env = self.env
-        env.reset()
-        per_step = torch.zeros((T_STEPS, env.num_games, env.num_players), dtype=torch.int32, device=env.device)
-        keep = torch.tensor([(self.seats_mask >> p) & 1 for p in range(env.num_players)], device=env.device,
-                            dtype=torch.bool)
-        for t in range(T_STEPS):
-            acts = self.decide(T_STEPS - t, record=record)
-            if self.M < env.num_players:
-                acts = torch.where(keep[None, :], acts, self._random_moves())
-            rew, done, inv = env.step(acts)
-            per_step[t] = rew
+        per_step = self._play_steps(record)
         self.end_episode(per_step)
         return per_step.sum(dim=0), per_step
 
@@ -322,3 +309,31 @@ class BatchedDQN(BatchedPUCT):
             optimizer.step()
             losses.append(loss.detach())
         return losses
+
+    # ------------------------------------------------------------ the league's protocol (puct.BatchedPUCT)
+    closes_round = True
+
+    @classmethod
+    def from_agent(cls, env, agent, *, seed, net_dtype, slots, seats):
+        """T_STEPS minibatch updates per round (the reference's learn calls per game), each on at least one
+        row per slot.  agent.history, the drop-in's host buffer, stays unused (copy_player's deepcopy works)."""
+        from .agents.dqn import DQN_PRBAgent
+
+        return cls(env, agent.dqn_net_local, target_net=getattr(agent, "dqn_net_target", None),
+                   prioritised=isinstance(agent, DQN_PRBAgent), gamma=agent.gamma, eps_func=agent.eps_func,
+                   minibatch=max(int(agent.minibatch), slots), updates=T_STEPS,
+                   retrain_interval=getattr(agent, "retrain_interval", 4), tau=getattr(agent, "tau", 1e-2),
+                   capacity=league_capacity(agent.history.max_length, seats), seed=seed, net_dtype=net_dtype,
+                   max_decisions=slots)
+
+    def begin_round(self, dec, agent, train):
+        """training: eps_func(rounds finished); else the agent's own eps"""
+        super().begin_round(dec, agent, train)
+        self.training, self.eps = train, agent.eps
+
+    def end_round(self, per_step):
+        self.end_episode(per_step)  # terminal observation, lagged rewards, rows into the replay
+
+    def learn_round(self, optimizer, per_step, updates_per_round):
+        """its own schedule: `updates` minibatches per round, every one counted"""
+        return len(self.learn(optimizer)) if self.D else None

@@ -47,6 +47,14 @@ Training (train=True, like run.py's agent.train()): after each round every
 net agent takes one Adam step on its loss summed over the round's games
 (the reference steps once per game: puct.py / acer.py document the batched
 losses).  Nets move to the tournament's device.
+
+The engines are driven through one protocol (puct.BatchedPUCT, overridden
+where an engine differs; ENGINES maps a net kind to its class): from_agent
+builds the engine of a drop-in agent (hyper-parameters, replay size); a round
+is begin_round(dec, agent, train), ten decide(n, record=train), end_round
+(engines with `closes_round`: DQN stores the round's transitions) and
+learn_round -> the optimiser steps to count; inherit(parent) hands a clone's
+engine what its parent's keeps (ACER: the replay).
 """
 import copy
 import ctypes
@@ -57,6 +65,10 @@ import numpy as np
 import torch
 
 from . import _native as nat
+from .acer import BatchedACER
+from .dqn import BatchedDQN
+from .puct import BatchedPUCT, BatchedPUCTCustomed
+from .reinforce import BatchedReinforce
 from .vec_env import VecSechsNimmtEnv
 
 logger = logging.getLogger(__name__)
@@ -66,6 +78,8 @@ KIND_RANDOM, KIND_MCS, KIND_PUCT, KIND_CUSTOMED, KIND_ACER = "random", "mcs", "p
 KIND_REINFORCE = "reinforce"
 KIND_DQN = "dqn"
 NET_KINDS = (KIND_PUCT, KIND_CUSTOMED, KIND_ACER, KIND_REINFORCE, KIND_DQN)
+ENGINES = {KIND_PUCT: BatchedPUCT, KIND_CUSTOMED: BatchedPUCTCustomed, KIND_ACER: BatchedACER,
+           KIND_REINFORCE: BatchedReinforce, KIND_DQN: BatchedDQN}
 T_STEPS = 10
 
 
@@ -379,60 +393,21 @@ class BatchedTournament:
                     eng = self._engine(n)
                     parent = self._inherit.pop(n, None)
                     if parent is not None:
-                        inherit_replay(eng, parent)
+                        eng.inherit(parent)
                 keep[n] = eng
         self.engines = keep
         self._inherit.clear()
 
     def _engine(self, name):
         """the batched engine of one net agent over this handle (decision-list mode)"""
-        from .acer import BatchedACER
-        from .dqn import BatchedDQN
-        from .puct import BatchedPUCT, BatchedPUCTCustomed
-        from .reinforce import BatchedReinforce
-
-        agent, kind, env = self.agents[name], self.kinds[name], self.env
+        agent, env = self.agents[name], self.env
         agent.to(env.device)
         agent.device = env.device
         seed = (self.seed * 1000003 + self.names.index(name) * 7919 + self.game_offset) & (2**62 - 1)
-        B = self.num_slots
-        if kind == KIND_PUCT:
-            return BatchedPUCT(env, agent.actor, mc_per_card=agent.mc_per_card, mc_max=agent.mc_max,
-                               c_puct=getattr(agent, "c_puct", 2.0), seed=seed, puct_root=agent._puct_root,
-                               net_dtype=self.net_dtype, mcs_num_cards=agent.num_cards, max_decisions=B)
-            # whole rollouts per kernel (sn_puct_rollouts) since round 6: 0.783 vs 0.822-0.827 s per run.py
-            # league round against a launch per step (DESIGN.md §4, gpurun_out/r06_mixed3)
-        if kind == KIND_CUSTOMED:
-            return BatchedPUCTCustomed(env, agent.actor, net_dtype=self.net_dtype, seed=seed, max_decisions=B)
-        if kind == KIND_REINFORCE:
-            return BatchedReinforce(env, agent.actor, net_dtype=self.net_dtype, seed=seed, gamma=agent.gamma,
-                                    r_factor=agent.r_factor, actor_weight=agent.actor_weight,
-                                    entropy_weight=agent.entropy_weight, max_decisions=B)
         K = max(1, len(self.active_agents()))
-        seats = B * (self.min_players + self.max_players) / 2.0 / K  # expected seats of this agent per round
-        if kind == KIND_DQN:
-            # T_STEPS minibatch updates per round (the reference's learn calls per game), each on at least
-            # one row per slot; a ring of two expected rounds of transitions at least (a power of two).
-            # agent.history, the drop-in's host buffer, stays unused (copy_player's deepcopy keeps working).
-            from .agents.dqn import DQN_PRBAgent
-
-            need = max(int(agent.history.max_length or 0), int(2 * T_STEPS * seats), 2)
-            capacity = 1 << (need - 1).bit_length()
-            return BatchedDQN(env, agent.dqn_net_local, target_net=getattr(agent, "dqn_net_target", None),
-                              prioritised=isinstance(agent, DQN_PRBAgent), gamma=agent.gamma, eps_func=agent.eps_func,
-                              minibatch=max(int(agent.minibatch), B), updates=T_STEPS,
-                              retrain_interval=getattr(agent, "retrain_interval", 4), tau=getattr(agent, "tau", 1e-2),
-                              capacity=capacity, seed=seed, net_dtype=self.net_dtype, max_decisions=B)
-        # replay rounds: enough that the stored sequences (every seat of the
-        # agent in each kept round, ceil(10 / rollout_len) per seat) pass
-        # max(warmup, minibatch), from the expected seats per round
-        chunks = -(-T_STEPS // int(agent.rollout_len))
-        need = max(int(agent.warmup), int(agent.batchsize)) + 1
-        capacity = max(2, int(-(-need // max(1.0, seats * chunks))) + 1)
-        return BatchedACER(env, agent.actor_critic, net_dtype=self.net_dtype, seed=seed, gamma=agent.gamma,
-                           rollout_len=agent.rollout_len, minibatch=agent.batchsize, truncate=agent.truncate,
-                           warmup=agent.warmup, r_factor=agent.r_factor, critic_weight=agent.critic_weight,
-                           capacity=capacity, log_epsilon=agent.log_epsilon, max_decisions=B)
+        seats = self.num_slots * (self.min_players + self.max_players) / 2.0 / K  # expected seats of this agent per round
+        return ENGINES[self.kinds[name]].from_agent(env, agent, seed=seed, net_dtype=self.net_dtype,
+                                                    slots=self.num_slots, seats=seats)
 
     # ------------------------------------------------------------ games (tournament.py:132-138)
     def play_games(self, games=1, rewards=False):
@@ -502,17 +477,12 @@ class BatchedTournament:
     def _round(self):
         """one game per slot: sn_reset (seat draw + deal), then 10 x [net
         agents' engines on their seats -> sn_league_step]"""
-        from .dqn import BatchedDQN
-
         env, L, st = self.env, nat.lib(), self.env._stream()
         B, N, dev = self.num_slots, self.max_players, env.device
         self._phase_events = []
         with self._phase("reset (seat draw + deal) + decision lists"):
             nat.check(L.sn_reset(env._h, None, st), "sn_reset")  # Tournament.play_game: seats, then the deal
             self._use_decisions()
-        dqn = {n: e for n, e in self.engines.items() if isinstance(e, BatchedDQN)}
-        for name, eng in dqn.items():  # training: eps_func(rounds finished); else the agent's own eps
-            eng.training, eng.eps = self.train, self.agents[name].eps
         acts = torch.zeros((B, N), dtype=torch.int32, device=dev)
         per_step = torch.zeros((T_STEPS, B, N), dtype=torch.int32, device=dev)
         rec = torch.zeros((B, 1 + N), dtype=torch.int32, device=dev)
@@ -532,9 +502,10 @@ class BatchedTournament:
                 nat.check(L.sn_league_step(env._h, nat.ptr(acts), nat.ptr(per_step[t]), None,
                                            nat.ptr(rec) if t == T_STEPS - 1 else None, nat.ptr(invalid[t]),
                                            nat.ptr(status), st), "sn_league_step")
-        for name, eng in dqn.items():
-            with self._phase(f"store {name}"):
-                eng.end_episode(per_step)  # terminal observation, lagged rewards, rows into the replay
+        for name, eng in self.engines.items():
+            if eng.closes_round:
+                with self._phase(f"store {name}"):
+                    eng.end_round(per_step)
         if self.engines:  # external seats played: an illegal card fails the round (sechs.h) -- checked once
             # per round, not per step: a host read-back per step kept the host from enqueueing the next
             # step's searches while the GPU ran this one
@@ -557,48 +528,18 @@ class BatchedTournament:
             flat = ids.reshape(-1)
             act = self.active_agents()
             for name, eng in self.engines.items():
-                eng.use_decisions(torch.nonzero(flat == act.index(name)).flatten())
-                eng.decisions = []
+                eng.begin_round(torch.nonzero(flat == act.index(name)).flatten(), self.agents[name], self.train)
 
     def _learn(self, per_step):
-        """one Adam step per net agent on its loss over the round's games"""
-        from .acer import BatchedACER
-        from .dqn import BatchedDQN
-        from .puct import BatchedPUCTCustomed
-        from .reinforce import BatchedReinforce
-
+        """every net agent trains on the round (learn_round: its engine's own schedule)"""
         for name, eng in self.engines.items():
             agent = self.agents[name]
             if agent.optimizer is None:
                 agent.train()
             with self._phase(f"learn {name}"):
-                if isinstance(eng, BatchedACER):
-                    if eng.D:
-                        eng.record_rewards(per_step)
-                        eng.learn(agent.optimizer)
-                    continue
-                if isinstance(eng, BatchedDQN):  # its own schedule too: `updates` minibatches per round
-                    if eng.D:
-                        steps = len(eng.learn(agent.optimizer))
-                        self.optimizer_steps[name] = self.optimizer_steps.get(name, 0) + steps
-                    continue
-                if eng.D == 0 or not eng.decisions:
-                    continue
-                # one decider per game of this agent (a game seats distinct agents):
-                # k contiguous decider ranges = k chunks of games
-                D = int(eng.D)
-                k = D if self.updates_per_round == "games" else min(int(self.updates_per_round), D)
-                bounds = [D * c // k for c in range(k + 1)]
-                for d0, d1 in zip(bounds[:-1], bounds[1:]):
-                    if isinstance(eng, (BatchedPUCTCustomed, BatchedReinforce)):
-                        loss = eng.loss(per_step, d0, d1) if k > 1 else eng.loss(per_step)
-                    else:
-                        loss = eng.policy_loss(d0, d1) if k > 1 else eng.policy_loss()
-                    agent.optimizer.zero_grad()
-                    loss.backward()
-                    agent.optimizer.step()
-                    self.optimizer_steps[name] = self.optimizer_steps.get(name, 0) + 1
-                eng.decisions = []
+                steps = eng.learn_round(agent.optimizer, per_step, self.updates_per_round)
+            if steps is not None:
+                self.optimizer_steps[name] = self.optimizer_steps.get(name, 0) + steps
 
     def seats(self):
         """(k [slots], active agent index [slots, max_players]) of every slot's current game"""
@@ -778,31 +719,6 @@ class BatchedTournament:
         if self.env is not None:
             self.env.close()
             self.env = None
-
-
-def inherit_replay(dst, src):
-    """a clone's ACER engine starts from its parent's replay, as the
-    reference's copy_player carries the agent's history through its
-    torch.save round trip (tournament.py:54-60, the agent's
-    SequentialHistory): the parent's most recent episodes, oldest first, up
-    to the clone's capacity.  Other engines keep nothing across rounds."""
-    from .acer import BatchedACER
-
-    if not (isinstance(dst, BatchedACER) and isinstance(src, BatchedACER)):
-        return
-    if dst.rep_rows.shape[1:] != src.rep_rows.shape[1:]:
-        return
-    n = min(src.episodes, src.capacity, dst.capacity)
-    with torch.no_grad():
-        for k in range(n):
-            e = src.episodes - n + k
-            a, b = e % src.capacity, k % dst.capacity
-            dst.rep_rows[b].copy_(src.rep_rows[a])
-            dst.rep_act[b].copy_(src.rep_act[a])
-            dst.rep_logp[b].copy_(src.rep_logp[a])
-            dst.rep_rew[b].copy_(src.rep_rew[a])
-            dst.rep_nd[b] = src.rep_nd[a]
-    dst.episodes = n
 
 
 def league_agent_stats(records, num_agents, max_players):

@@ -149,7 +149,7 @@ class BatchedPUCT:
         # tournament mode (max_decisions given): the deciding seats are a
         # decision list (use_decisions: g * N + p of this agent's seats in the
         # slots' current games), at most max_decisions of them
-        self.dec = None
+        self.dec, self._flat = None, None
         if max_decisions is not None:
             self.D = 0
         self.D_max = B * self.M if max_decisions is None else int(max_decisions)
@@ -229,6 +229,20 @@ class BatchedPUCT:
         assert dec.numel() <= self.D_max, "more decisions than max_decisions"
         self.dec, self.D = dec, int(dec.numel())
 
+    def decider_index(self):
+        """flat g * N + p of every decision, in decision order"""
+        if self.dec is not None:
+            return self.dec.long()
+        if self._flat is None:
+            N = self.env.num_players
+            seats = torch.tensor([p for p in range(N) if (self.seats_mask >> p) & 1], device=self.env.device)
+            self._flat = (torch.arange(self.env.num_games, device=self.env.device)[:, None] * N + seats[None, :]).reshape(-1)
+        return self._flat
+
+    def decider_rewards(self, per_step):
+        """per_step [T, B, N] -> [T, D]: the deciding seats' rewards in decision order"""
+        return per_step.reshape(per_step.shape[0], -1)[:, self.decider_index()]
+
     def _params(self, n, rollout=0, step_dev=False):
         q = nat.SnPuct()
         if self.dec is not None:
@@ -245,6 +259,14 @@ class BatchedPUCT:
         nat.check(nat.lib().sn_mcs_memorize(self.env._h, nat.ptr(self.avail), self.mcs_num_cards, self.env._stream()),
                   "sn_mcs_memorize")
 
+    def _root_rows(self, q, n):
+        """the normalised candidate rows [D * n, ROW] of every decision, in net_dtype"""
+        rows = torch.empty((self.D * n, ROW), dtype=self.net_dtype, device=self.env.device)
+        bf16 = int(self.net_dtype == torch.bfloat16)
+        nat.check(nat.lib().sn_puct_root_rows(self.env._h, ctypes_ref(q), nat.ptr(rows), bf16, self.env._stream()),
+                  "sn_puct_root_rows")
+        return rows
+
     def decide(self, n, memorize=True, record=False):
         """Search every deciding seat at hand size n; returns actions [B, N]
         (int32, deciding seats filled in)."""
@@ -254,12 +276,10 @@ class BatchedPUCT:
         if self.D == 0:  # tournament mode: this agent has no seat in any current game
             self.step_id += 1
             return self.actions
-        bf16 = int(self.net_dtype == torch.bfloat16)
         q = self._params(n)
         if n > 1:
             self.sync_net()
-            rows = torch.empty((self.D * n, ROW), dtype=self.net_dtype, device=self.env.device)
-            nat.check(L.sn_puct_root_rows(h, ctypes_ref(q), nat.ptr(rows), bf16, st), "sn_puct_root_rows")
+            rows = self._root_rows(q, n)
             nat.check(L.sn_puct_init(h, ctypes_ref(q), nat.ptr(self._logits(rows)), st), "sn_puct_init")
             if self.graph:
                 # the same 32-bit counter as the eager path's q.step, as int32 bits
@@ -386,23 +406,24 @@ class BatchedPUCT:
         self.rows_evaluated = before
         return g, rows
 
-    def play_episode(self, others=None, record=False):
-        """One whole game of every env game; deciding seats search, the other
-        seats (if any) play DrunkHamster moves in-kernel.  Returns the summed
-        rewards [B, N] int32."""
+    def _play_steps(self, record):
+        """reset, then the ten steps: the deciding seats play decide()'s moves, the other seats (if any)
+        uniform legal ones; returns the per-step rewards [10, B, N] int32"""
         env = self.env
         env.reset()
-        total = torch.zeros((env.num_games, env.num_players), dtype=torch.int32, device=env.device)
+        N = env.num_players
+        per_step = torch.zeros((10, env.num_games, N), dtype=torch.int32, device=env.device)
+        keep = torch.tensor([(self.seats_mask >> p) & 1 for p in range(N)], device=env.device, dtype=torch.bool)
         for t in range(10):
             acts = self.decide(10 - t, record=record)
-            if self.M < env.num_players:
-                rnd = self._random_moves()
-                keep = torch.tensor([(self.seats_mask >> p) & 1 for p in range(env.num_players)], device=env.device,
-                                    dtype=torch.bool)
-                acts = torch.where(keep[None, :], acts, rnd)
-            rew, done, inv = env.step(acts)
-            total += rew
-        return total
+            if self.M < N:
+                acts = torch.where(keep[None, :], acts, self._random_moves())
+            per_step[t] = env.step(acts)[0]
+        return per_step
+
+    def play_episode(self, others=None, record=False):
+        """One whole game of every env game (_play_steps); returns the summed rewards [B, N] int32."""
+        return self._play_steps(record).sum(dim=0, dtype=torch.int32)
 
     def _random_moves(self):
         """uniform legal moves for the non-deciding seats (host-side torch RNG)"""
@@ -426,6 +447,48 @@ class BatchedPUCT:
             logp = torch.log_softmax(logits.reshape(-1, n), dim=1)
             loss = loss - logp.gather(1, best[:, None]).sum()
         return loss
+
+    # ------------------------------------------------------------ the league's protocol (league.py)
+    closes_round = False  # end_round does work: the league times it as its "store" phase
+
+    @classmethod
+    def from_agent(cls, env, agent, *, seed, net_dtype, slots, seats):
+        """the tournament-mode engine of a drop-in agent: at most `slots` decisions per step; `seats`,
+        the agent's expected seats per round, sizes the replay of the engines that keep one"""
+        return cls(env, agent.actor, mc_per_card=agent.mc_per_card, mc_max=agent.mc_max,
+                   c_puct=getattr(agent, "c_puct", 2.0), seed=seed, puct_root=agent._puct_root, net_dtype=net_dtype,
+                   mcs_num_cards=agent.num_cards, max_decisions=slots)
+
+    def begin_round(self, dec, agent, train):
+        """a round starts: `dec`, this agent's seats in the slots' new games"""
+        self.use_decisions(dec)
+        self.decisions = []
+
+    def end_round(self, per_step):
+        """the round's ten steps are played (per_step [10, B, N] int32)"""
+
+    def round_loss(self, per_step, *span):
+        """the loss learn_round steps on, over deciders `span` = (d0, d1) or all of them"""
+        return self.policy_loss(*span)
+
+    def learn_round(self, optimizer, per_step, updates_per_round):
+        """train on the round: one optimiser step per loss of k contiguous decider ranges (a decider per
+        game of this agent: k chunks of games; "games": every game).  Returns the steps to count, or None."""
+        if self.D == 0 or not self.decisions:
+            return None
+        D = int(self.D)
+        k = D if updates_per_round == "games" else min(int(updates_per_round), D)
+        bounds = [D * c // k for c in range(k + 1)]
+        for span in zip(bounds[:-1], bounds[1:]):
+            loss = self.round_loss(per_step, *(span if k > 1 else ()))
+            optimizer.zero_grad()
+            loss.backward()
+            optimizer.step()
+        self.decisions = []
+        return k
+
+    def inherit(self, parent):
+        """a clone's engine takes over what its parent's engine keeps across rounds (nothing here)"""
 
 
 def decision_forwards(actor, decisions, d0, d1, dev):
@@ -484,11 +547,9 @@ class BatchedPUCTCustomed(BatchedPUCT):
         if self.D == 0:
             self.step_id += 1
             return self.actions
-        bf16 = int(self.net_dtype == torch.bfloat16)
         q = self._params(n)
         self.sync_net()
-        rows = torch.empty((self.D * n, ROW), dtype=self.net_dtype, device=self.env.device)
-        nat.check(L.sn_puct_root_rows(h, ctypes_ref(q), nat.ptr(rows), bf16, st), "sn_puct_root_rows")
+        rows = self._root_rows(q, n)
         with torch.no_grad():
             (heads,) = self._net(rows)
         self.rows_evaluated += rows.shape[0]
@@ -503,32 +564,19 @@ class BatchedPUCTCustomed(BatchedPUCT):
     def play_episode(self, others=None, record=False):
         """one whole game of every env game; returns (summed rewards [B, N]
         int32, per-step rewards [10, B, N] int32)"""
-        env = self.env
-        env.reset()
-        per_step = torch.zeros((10, env.num_games, env.num_players), dtype=torch.int32, device=env.device)
-        for t in range(10):
-            acts = self.decide(10 - t, record=record)
-            if self.M < env.num_players:
-                keep = torch.tensor([(self.seats_mask >> p) & 1 for p in range(env.num_players)], device=env.device,
-                                    dtype=torch.bool)
-                acts = torch.where(keep[None, :], acts, self._random_moves())
-            rew, done, inv = env.step(acts)
-            per_step[t] = rew
-        self.episode_rewards = per_step
+        self.episode_rewards = per_step = self._play_steps(record)
         return per_step.sum(dim=0), per_step
 
-    def _decider_rewards(self, per_step):
-        if self.dec is not None:  # tournament mode: the decision list's seats
-            return per_step.reshape(per_step.shape[0], -1)[:, self.dec.long()]
-        seats = [p for p in range(self.env.num_players) if (self.seats_mask >> p) & 1]
-        return per_step[:, :, seats].reshape(per_step.shape[0], -1)  # [10, D] in decision order
+    @classmethod
+    def from_agent(cls, env, agent, *, seed, net_dtype, slots, seats):
+        return cls(env, agent.actor, net_dtype=net_dtype, seed=seed, max_decisions=slots)
 
     def loss(self, per_step=None, d0=0, d1=None):
         """reference loss of the recorded episode (mcts.py:431-451), summed over
         the games of deciders [d0, d1) (all by default)"""
         per_step = self.episode_rewards if per_step is None else per_step
         dev = self.actor_device()
-        target = self._decider_rewards(per_step)[:-1].sum(dim=0).float().to(dev)  # [D]
+        target = self.decider_rewards(per_step)[:-1].sum(dim=0).float().to(dev)  # [D]
         target = target[d0:d1]
         logps, values = [], []
         for (out,), n, best in decision_forwards(self.actor, self.decisions, d0, d1, dev):
@@ -541,6 +589,8 @@ class BatchedPUCTCustomed(BatchedPUCT):
         outcome_loss = ((values - target[:, None]) ** 2).mean(dim=1)
         policy_loss = -logps.sum(dim=1)
         return (outcome_loss + policy_loss).sum()
+
+    round_loss = loss  # what learn_round steps on
 
 
 def ctypes_ref(q):

@@ -21,7 +21,7 @@ import numpy as np
 import torch
 
 from . import _native as nat
-from .puct import ROW, BatchedPUCT, ctypes_ref, decision_forwards, make_actor
+from .puct import BatchedPUCT, ctypes_ref, decision_forwards, make_actor
 
 
 class BatchedReinforce(BatchedPUCT):
@@ -41,11 +41,9 @@ class BatchedReinforce(BatchedPUCT):
         if self.D == 0:  # tournament mode: no seat of this agent in the current games
             self.step_id += 1
             return self.actions
-        bf16 = int(self.net_dtype == torch.bfloat16)
         q = self._params(n)
         self.sync_net()
-        rows = torch.empty((self.D * n, ROW), dtype=self.net_dtype, device=self.env.device)
-        nat.check(L.sn_puct_root_rows(h, ctypes_ref(q), nat.ptr(rows), bf16, st), "sn_puct_root_rows")
+        rows = self._root_rows(q, n)
         logits = self._logits(rows)
         nat.check(L.sn_policy_sample(h, ctypes_ref(q), nat.ptr(logits), nat.ptr(self.actions), nat.ptr(self.best_index),
                                      nat.ptr(self.log_prob), nat.ptr(self.entropy), st), "sn_policy_sample")
@@ -58,27 +56,17 @@ class BatchedReinforce(BatchedPUCT):
         """one whole game of every env game (non-deciding seats: uniform
         moves); returns (summed rewards [B, N] int32, per-step rewards
         [10, B, N] int32)"""
-        env = self.env
-        env.reset()
-        per_step = torch.zeros((10, env.num_games, env.num_players), dtype=torch.int32, device=env.device)
-        for t in range(10):
-            acts = self.decide(10 - t, record=record)
-            if self.M < env.num_players:
-                keep = torch.tensor([(self.seats_mask >> p) & 1 for p in range(env.num_players)], device=env.device,
-                                    dtype=torch.bool)
-                acts = torch.where(keep[None, :], acts, self._random_moves())
-            rew, done, inv = env.step(acts)
-            per_step[t] = rew
-        self.episode_rewards = per_step
+        self.episode_rewards = per_step = self._play_steps(record)
         return per_step.sum(dim=0), per_step
+
+    @classmethod
+    def from_agent(cls, env, agent, *, seed, net_dtype, slots, seats):
+        return cls(env, agent.actor, net_dtype=net_dtype, seed=seed, gamma=agent.gamma, r_factor=agent.r_factor,
+                   actor_weight=agent.actor_weight, entropy_weight=agent.entropy_weight, max_decisions=slots)
 
     def returns(self, per_step):
         """discounted returns [D, T] of the rewards learn() would see"""
-        if self.dec is not None:  # tournament mode: the decision list's seats
-            r = per_step.reshape(per_step.shape[0], -1)[:, self.dec.long()].T.double() * self.r_factor
-        else:
-            seats = [p for p in range(self.env.num_players) if (self.seats_mask >> p) & 1]
-            r = per_step[:, :, seats].reshape(per_step.shape[0], -1).T.double() * self.r_factor  # [D, T]
+        r = self.decider_rewards(per_step).T.double() * self.r_factor  # [D, T]
         seen = torch.zeros_like(r)
         seen[:, 1:] = r[:, :-1]  # learn() at step t gets step t-1's reward
         G = torch.zeros_like(seen)
@@ -105,3 +93,5 @@ class BatchedReinforce(BatchedPUCT):
         actor_loss = -(disc[None, :] * G * logps).sum()
         entropy_loss = -ents.sum()
         return self.actor_weight * actor_loss + self.entropy_weight * entropy_loss
+
+    round_loss = loss  # what learn_round steps on

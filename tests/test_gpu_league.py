@@ -650,3 +650,35 @@ def test_clone_inherits_the_acer_replay_and_plays():
     seated = (ids == t.active_agents().index("acer_c")) & (torch.arange(4, device=ids.device)[None, :] < kk[:, None])
     assert bool(seated.any()) and "r0" not in t.active_agents()
     t.close()
+
+
+def test_one_round_protocol_drives_every_engine_kind():
+    """one agent of every net kind beside an MCS and a DrunkHamster seat: the
+    league drives them all through the same protocol (begin_round, decide,
+    end_round, learn_round, inherit) -- every move legal, the optimiser steps
+    counted for the engines that count them, ACER's and DQN's rounds closed,
+    the `store` phase DQN's alone, and clones' engines inheriting by kind"""
+    from rl_6_nimmt import agents as A
+    from rl_6_nimmt.league import BatchedTournament
+
+    torch.manual_seed(4)
+    t = BatchedTournament(48, 2, 4, seed=9, rng="numpy", fused=False, train=True)
+    nets = {"p": A.PUCTAgent(mc_max=6), "c": A.PUCTCustomedAgent(mc_max=6), "r": A.BatchedReinforceAgent(),
+            "a": A.BatchedACERAgent(), "q": A.DDQN_PRBAgent(history_length=64, minibatch=16)}
+    for n, a in nets.items():
+        t.add_player(n, a)
+    t.add_player("m", A.MCSAgent(mc_max=6))
+    t.add_player("x")
+    t.phase_timing = True
+    t.play_games(1)  # an illegal move of an engine would raise in the round
+    t.play_games(1)
+    assert set(t.optimizer_steps) == {"p", "c", "r", "q"} and all(v > 0 for v in t.optimizer_steps.values())
+    assert t.engines["a"].episodes == 2 and len(t.engines["q"].eps_history) == 2
+    assert {k for k in t.phase_ms if k.startswith("store ")} == {"store q"}
+    assert {f"decide {n}" for n in nets} | {f"learn {n}" for n in nets} <= set(t.phase_ms)
+    t.copy_player("a", "a_c")
+    t.copy_player("r", "r_c")
+    t._configure()  # what the next game does first
+    assert t.engines["a_c"].episodes > 0 and t.engines["r_c"].decisions == []
+    assert t.env.pipe_errors() == 0
+    t.close()
