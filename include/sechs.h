@@ -614,6 +614,40 @@ sn_status sn_dqn_pack(int64_t T, int64_t D, const void* obs_i8, const int32_t* a
    not_done [n] f32 = 1 - done.  Each output may be NULL. */
 sn_status sn_dqn_unpack(int64_t n, const void* rows, float* states, float* next_states, int64_t* action,
                         float* reward, float* not_done, void* stream);
+/* k_dqn_select for a duelling net (DuellingDQNNet, utils/nets.py:135-144) over
+   its padded head output, read in place: heads [D][stride] f32 with V in
+   column v_col and A in the 104 columns a_off .. a_off + 103 (both inside the
+   row, V outside A).  Per decision Q_c = V + (A_c - mean) in fp32, unfused,
+   mean = sum / 104.0f, the sum of A over all 104 actions in this order: four
+   partial sums s_k over the columns c = k (mod 4), each ascending, then
+   (s_0 + s_1) + (s_2 + s_3).  Everything else is sn_dqn_select's: the same
+   Philox keys, the first maximum over the ascending hand, value = Q of the
+   choice (-1 when exploring), a card byte past the hand ends the scan.  Rows
+   whose A starts 16-byte aligned (heads + a_off aligned, stride a multiple of
+   4) are read with 16-byte loads, others with 4-byte loads: the same result. */
+sn_status sn_dqn_select_duel(sn_env* env, const sn_puct* q, const float* heads, int64_t stride, int64_t v_col,
+                             int64_t a_off, double eps, int32_t* actions, int32_t* index, float* value, void* stream);
+/* The n-step transitions of one episode (DQN_NStep_Agent._store and
+   _finish_episode, agents/dqn.py:264-301), T <= 10 steps, n >= 1 (else
+   SN_EINVAL).  Inputs as sn_dqn_pack's; gpow.v[i] = gamma ** i as the host
+   computes it (CPython's float power: no device pow takes part).  Row (s, d),
+   with m = min(n, T - s):
+     bytes 0-47 state = obs[s], 48-95 next_state = obs[min(s + n, T)],
+     96 action, 97 done = (s + n > T) or (n == 1 and s == T - 1), 98 hand size,
+     99 m, 100-103 r_s int32, 104-107 the n-step return as f32: accumulated in
+     f64 from 0.0, left to right, acc = acc + (double)r_{s+i} * gpow.v[i] for
+     i < m (unfused), rounded once; 108-111 zero.
+   Kept from the reference: for n > 1 the row s = T - n points at the terminal
+   observation with done 0. */
+#define SN_DQN_T_STEPS 10
+typedef struct {
+    double v[SN_DQN_T_STEPS];
+} sn_dqn_gpow;
+sn_status sn_dqn_pack_nstep(int64_t T, int64_t D, int64_t n, sn_dqn_gpow gpow, const void* obs_i8,
+                            const int32_t* actions, const int32_t* rewards_seen, void* rows, void* stream);
+/* sn_dqn_unpack with reward = the f32 n-step return at byte 104 */
+sn_status sn_dqn_unpack_nstep(int64_t n, const void* rows, float* states, float* next_states, int64_t* action,
+                              float* reward, float* not_done, void* stream);
 /* Both Bellman targets over q_next_local / q_next_target [n][stride] f32
    (stride >= 104; the maximum runs over all 104 actions, unmasked, as in the
    reference).  q_next_target NULL: DQNVanilla._calc_reward
@@ -622,7 +656,7 @@ sn_status sn_dqn_unpack(int64_t n, const void* rows, float* states, float* next_
    (Q_target(s')[argmax_a Q_local(s')] * not_done), the lowest index on ties.
    fp32 in exactly that operation order, unfused; gamma is rounded to f32
    once, as torch rounds the Python scalar: bit-equal to the torch fp32
-   expression on the same tensors. */
+   expression on the same tensors.  The n-step agents pass gamma ** n_steps. */
 sn_status sn_dqn_target(int64_t n, const float* q_next_local, const float* q_next_target, int64_t stride,
                         const float* reward, const float* not_done, double gamma, float* target, void* stream);
 

@@ -1417,6 +1417,70 @@ __global__ void k_dqn_select(DevState s, PuctArgs a, const float* qvals, int64_t
     if (value) value[d] = v;
 }
 
+// k_dqn_select over a duelling net's head output read in place: heads
+// [D][stride] f32 with V in column v_col and A in the 104 columns from a_off.
+// Q_c = V + (A_c - mean A) as torch evaluates DuellingDQNNet.forward in fp32,
+// unfused; mean = sum / 104.0f with the sum taken in this fixed order: four
+// partial sums s_k over the columns c = k (mod 4), each ascending in c, then
+// (s_0 + s_1) + (s_2 + s_3).  VEC: every row's A starts 16-byte aligned and
+// is read as 26 float4; else scalar loads, the same order.  Philox keys, the
+// exploring branch and the short-hand guard are k_dqn_select's.  One lane per
+// decision.
+template <bool VEC>
+__global__ void k_dqn_select_duel(DevState s, PuctArgs a, const float* heads, int64_t stride, int v_col, int a_off,
+                                  double eps, int32_t* actions, int32_t* index, float* value) {
+#pragma clang fp contract(off)
+    const int64_t d = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (d >= a.D) return;
+    int64_t g;
+    int p;
+    dec_to_gp(a, d, g, p);
+    const Hand h = load_hand(s, p, g);
+    const uint64_t gid = s.game_offset + (uint64_t)g;
+    const uint64_t stream = ((uint64_t)(uint32_t)gid << 32) | ((uint64_t)p << 28) | (0xFFFFEull << 8);
+    const u32x4 o = philox4x32_10(0u, 0u, (uint32_t)stream, (uint32_t)(stream >> 32), a.seed_lo ^ puct_step_of(a),
+                                  a.seed_hi);
+    const float u1 = (float)(o.x >> 8) * (1.0f / 16777216.0f), u2 = (float)(o.y >> 8) * (1.0f / 16777216.0f);
+    int k;
+    float v;
+    if (eps <= 0.0 || (eps < 1.0 && (double)u1 > eps)) {
+        const float* x = heads + d * stride;
+        const float* adv = x + a_off;
+        float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+#pragma unroll 2
+        for (int j = 0; j < kDqnActions / 4; j++) {
+            float4 w;
+            if (VEC)
+                w = reinterpret_cast<const float4*>(adv)[j];
+            else
+                w = float4{adv[4 * j], adv[4 * j + 1], adv[4 * j + 2], adv[4 * j + 3]};
+            s0 = s0 + w.x;
+            s1 = s1 + w.y;
+            s2 = s2 + w.z;
+            s3 = s3 + w.w;
+        }
+        const float sum = (s0 + s1) + (s2 + s3);
+        const float mean = sum / (float)kDqnActions;
+        const float V = x[v_col];
+        k = 0;
+        v = -1.f;
+        for (int j = 0; j < a.n; j++) {
+            const uint32_t c = hand_get(h, (uint32_t)j);
+            if (c >= (uint32_t)kDqnActions) break;  // a hand shorter than q->n: no load past the row
+            const float centred = adv[c] - mean;
+            const float q = V + centred;
+            if (j == 0 || q > v) v = q, k = j;
+        }
+    } else {  // random.choice(legal)
+        k = (int)(u2 * (float)a.n);
+        k = k < a.n ? k : a.n - 1;
+        v = -1.f;
+    }
+    actions[g * s.N + p] = (int32_t)hand_get(h, (uint32_t)k);
+    if (index) index[d] = k;
+    if (value) value[d] = v;
+}
+
 // Replay rows of one episode: row (t, d) = [obs[t][d] | obs[t+1][d] | action,
 // done, hand size, 0 | reward i32 | 0, 0].  One lane per 16-byte piece,
 // consecutive lanes on consecutive pieces of a row (as k_per_store).
@@ -1440,9 +1504,57 @@ __global__ void k_dqn_pack(int64_t T, int64_t D, const u32x4* __restrict__ obs, 
     rows[e] = v;
 }
 
+// The n-step rows of one episode (DQN_NStep_Agent._store / _finish_episode,
+// agents/dqn.py:264-301): row (s, d) = [obs[s][d] | obs[min(s + n, T)][d] |
+// action, done, hand size, m | r_s i32 | n-step return f32 | 0] with
+// m = min(n, T - s) rewards summed and done = s + n > T, or the last step's
+// own flag when n = 1.  The return accumulates in f64 from 0.0, left to
+// right, acc = acc + (double)r_{s+i} * gpow[i] unfused (Python's sum of
+// r * gamma ** i; gpow holds the host's gamma ** i), and is rounded to f32
+// once.  One lane per 16-byte piece.
+struct DqnGpow {
+    double v[SN_DQN_T_STEPS];
+};
+__global__ void k_dqn_pack_nstep(int64_t T, int64_t D, int n, DqnGpow gpow, const u32x4* __restrict__ obs,
+                                 const int32_t* __restrict__ actions, const int32_t* __restrict__ rewards_seen,
+                                 u32x4* __restrict__ rows) {
+#pragma clang fp contract(off)
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= T * D * kDqnPieces) return;
+    const int64_t r = e / kDqnPieces;
+    const int c = (int)(e - r * kDqnPieces);
+    const int64_t t = r / D;
+    const int64_t left = T - t;  // 1..T <= SN_DQN_T_STEPS
+    const int m = (int64_t)n < left ? n : (int)left;
+    u32x4 v;
+    if (c < 3) {
+        v = obs[r * 3 + c];
+    } else if (c < 6) {
+        v = obs[(r + (int64_t)m * D) * 3 + (c - 3)];  // obs[min(t + n, T)][d] lies m * D rows on
+    } else {
+        const u32x4 h = obs[r * 3];  // hand bytes 0..9: the cards held are >= 0
+        const uint32_t neg = (h.x & 0x80808080u) | ((h.y & 0x80808080u) >> 1) | ((h.z & 0x00008080u) >> 2);
+        const uint32_t hand = 10u - (uint32_t)__builtin_popcount(neg);
+        const uint32_t done = ((int64_t)n > left || (n == 1 && left == 1)) ? 1u : 0u;
+        double acc = 0.0;
+#pragma unroll
+        for (int i = 0; i < SN_DQN_T_STEPS; i++) {
+            if (i < m) {
+                const double term = (double)rewards_seen[r + (int64_t)i * D] * gpow.v[i];
+                acc = acc + term;
+            }
+        }
+        v = u32x4{((uint32_t)actions[r] & 0xFFu) | (done << 8) | (hand << 16) | ((uint32_t)m << 24),
+                  (uint32_t)rewards_seen[r], __float_as_uint((float)acc), 0u};
+    }
+    rows[e] = v;
+}
+
 // the inverse for a sampled minibatch: fp32 states / next_states [n][48],
 // action [n] i64, reward [n] f32, not_done [n] f32 = 1 - done.  One lane per
-// 16-byte piece of a row.
+// 16-byte piece of a row.  NSTEP: the reward is the n-step return, the f32 at
+// byte 104 (k_dqn_pack_nstep); else the i32 at byte 100.
+template <bool NSTEP>
 __global__ void k_dqn_unpack(int64_t n, const u32x4* __restrict__ rows, float* __restrict__ states,
                              float* __restrict__ next_states, int64_t* __restrict__ action, float* __restrict__ reward,
                              float* __restrict__ not_done) {
@@ -1457,7 +1569,7 @@ __global__ void k_dqn_unpack(int64_t n, const u32x4* __restrict__ rows, float* _
         if (next_states) piece_to_f32(v, next_states + r * kDqnObs + 16 * (c - 3));
     } else {
         if (action) action[r] = (int64_t)(v.x & 0xFFu);
-        if (reward) reward[r] = (float)(int32_t)v.y;
+        if (reward) reward[r] = NSTEP ? __uint_as_float(v.z) : (float)(int32_t)v.y;
         if (not_done) not_done[r] = ((v.x >> 8) & 0xFFu) ? 0.f : 1.f;
     }
 }
@@ -1812,7 +1924,56 @@ sn_status sn_dqn_unpack(int64_t n, const void* rows, float* states, float* next_
     if (n < 1 || n > 0x7FFFFFFF) return set_error(SN_EINVAL, "n must be in 1..2^31-1");
     if ((((uintptr_t)rows | (uintptr_t)states | (uintptr_t)next_states) & 15) != 0)
         return set_error(SN_EINVAL, "rows, states and next_states must be 16-byte aligned");
-    hipLaunchKernelGGL(k_dqn_unpack, dim3(grid_for(n * kDqnPieces)), dim3(kBlock), 0, (hipStream_t)stream, n,
+    hipLaunchKernelGGL(k_dqn_unpack<false>, dim3(grid_for(n * kDqnPieces)), dim3(kBlock), 0, (hipStream_t)stream, n,
+                       (const u32x4*)rows, states, next_states, action, reward, not_done);
+    HIP_TRY(hipGetLastError());
+    return SN_OK;
+}
+
+sn_status sn_dqn_select_duel(sn_env* e, const sn_puct* q, const float* heads, int64_t stride, int64_t v_col,
+                             int64_t a_off, double eps, int32_t* actions, int32_t* index, float* value, void* stream) {
+    if (!heads || !actions) return set_error(SN_EINVAL, "NULL argument");
+    if (a_off < 0 || v_col < 0 || a_off > stride - kDqnActions || v_col >= stride ||
+        (v_col >= a_off && v_col < a_off + kDqnActions))
+        return set_error(SN_EINVAL, "V and the 104 A columns must lie apart inside a row of `stride` floats");
+    if (stride > 0x7FFFFFFF) return set_error(SN_EINVAL, "stride must be < 2^31");
+    if (!(eps == eps)) return set_error(SN_EINVAL, "eps is NaN");
+    PuctArgs a{};
+    sn_status st = puct_args(e, q, a);
+    if (st != SN_OK) return st;
+    const bool vec = ((uintptr_t)(heads + a_off) & 15) == 0 && (stride & 3) == 0;
+    if (vec)
+        hipLaunchKernelGGL(k_dqn_select_duel<true>, dim3(grid_for(a.D)), dim3(kBlock), 0, (hipStream_t)stream, e->s, a,
+                           heads, stride, (int)v_col, (int)a_off, eps, actions, index, value);
+    else
+        hipLaunchKernelGGL(k_dqn_select_duel<false>, dim3(grid_for(a.D)), dim3(kBlock), 0, (hipStream_t)stream, e->s, a,
+                           heads, stride, (int)v_col, (int)a_off, eps, actions, index, value);
+    HIP_TRY(hipGetLastError());
+    return SN_OK;
+}
+
+sn_status sn_dqn_pack_nstep(int64_t T, int64_t D, int64_t n, sn_dqn_gpow gpow, const void* obs_i8,
+                            const int32_t* actions, const int32_t* rewards_seen, void* rows, void* stream) {
+    if (!obs_i8 || !actions || !rewards_seen || !rows) return set_error(SN_EINVAL, "NULL argument");
+    if (T < 1 || T > SN_DQN_T_STEPS) return set_error(SN_EINVAL, "T must be in 1..10");
+    if (n < 1 || n > 0x7FFFFFFF) return set_error(SN_EINVAL, "n must be in 1..2^31-1");
+    if (D < 1 || T > 0x7FFFFFFF / D) return set_error(SN_EINVAL, "T x D must be in 1..2^31-1");
+    if ((((uintptr_t)obs_i8 | (uintptr_t)rows) & 15) != 0) return set_error(SN_EINVAL, "obs_i8 and rows must be 16-byte aligned");
+    DqnGpow gp;
+    for (int i = 0; i < SN_DQN_T_STEPS; i++) gp.v[i] = gpow.v[i];
+    hipLaunchKernelGGL(k_dqn_pack_nstep, dim3(grid_for(T * D * kDqnPieces)), dim3(kBlock), 0, (hipStream_t)stream, T, D,
+                       (int)n, gp, (const u32x4*)obs_i8, actions, rewards_seen, (u32x4*)rows);
+    HIP_TRY(hipGetLastError());
+    return SN_OK;
+}
+
+sn_status sn_dqn_unpack_nstep(int64_t n, const void* rows, float* states, float* next_states, int64_t* action,
+                              float* reward, float* not_done, void* stream) {
+    if (!rows) return set_error(SN_EINVAL, "NULL argument");
+    if (n < 1 || n > 0x7FFFFFFF) return set_error(SN_EINVAL, "n must be in 1..2^31-1");
+    if ((((uintptr_t)rows | (uintptr_t)states | (uintptr_t)next_states) & 15) != 0)
+        return set_error(SN_EINVAL, "rows, states and next_states must be 16-byte aligned");
+    hipLaunchKernelGGL(k_dqn_unpack<true>, dim3(grid_for(n * kDqnPieces)), dim3(kBlock), 0, (hipStream_t)stream, n,
                        (const u32x4*)rows, states, next_states, action, reward, not_done);
     HIP_TRY(hipGetLastError());
     return SN_OK;

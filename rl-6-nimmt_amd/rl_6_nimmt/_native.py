@@ -54,6 +54,12 @@ class SnPuct(ctypes.Structure):
     ]
 
 
+class SnDqnGpow(ctypes.Structure):
+    """sn_dqn_gpow (include/sechs.h): gamma ** i for i < 10, passed by value"""
+
+    _fields_ = [("v", ctypes.c_double * 10)]
+
+
 # every symbol include/sechs.h declares, with its ctypes signature
 _P = ctypes.c_void_p
 _I = ctypes.c_int
@@ -125,6 +131,9 @@ SIGNATURES = {
     "sn_dqn_pack": ([_I64, _I64, _P, _P, _P, _P, _P], _I),
     "sn_dqn_unpack": ([_I64, _P, _P, _P, _P, _P, _P, _P], _I),
     "sn_dqn_target": ([_I64, _P, _P, _I64, _P, _P, ctypes.c_double, _P, _P], _I),
+    "sn_dqn_select_duel": ([_P, _P, _P, _I64, _I64, _I64, ctypes.c_double, _P, _P, _P, _P], _I),
+    "sn_dqn_pack_nstep": ([_I64, _I64, _I64, SnDqnGpow, _P, _P, _P, _P, _P], _I),
+    "sn_dqn_unpack_nstep": ([_I64, _P, _P, _P, _P, _P, _P, _P], _I),
 }
 
 

@@ -11,7 +11,11 @@ device prioritised replay (rl_6_nimmt/replay.py) and registered in
 DQN_AGENTS, not in AGENTS.  The batched league seats them through
 league.engine_kind -> "dqn" (dqn.BatchedDQN on the replay's payload ring);
 league.agent_kind, the registry's map, still raises NotImplementedError for
-them.  Not built: the duelling, noisy and n-step DQN variants and the human UI.
+them.  The duelling and n-step variants -- DuellingDQNAgent ("duelling_dqn"),
+DuellingDDQNAgent ("duelling_ddqn"), DuellingDDQN_PRBAgent
+("duelling_ddqn_prb"), DQN_NStep_Agent ("dqn_nstep"), D3QN_PRB_NStep
+("d3qn_prb_nstep") -- are registered in DQN_VARIANT_AGENTS and take the same
+seat.  Not built: the noisy DQN variants and the human UI.
 """
 from .base import Agent
 from .random import DrunkHamster
@@ -19,6 +23,7 @@ from .mcts import BaseMCAgent, MCSAgent, PolicyMCSAgent, PUCTAgent, PUCTCustomed
 from .policy import BatchedReinforceAgent
 from .actor_critic import BatchedACERAgent
 from .dqn import DQNVanilla, DDQNAgent, DQN_PRBAgent, DDQN_PRBAgent
+from .dqn import DuellingDQNAgent, DuellingDDQNAgent, DuellingDDQN_PRBAgent, DQN_NStep_Agent, D3QN_PRB_NStep
 
 HUMAN = "human"
 RANDOM_AGENT = "random"
@@ -28,6 +33,11 @@ DQN = "dqn"
 DDQN = "ddqn"
 DQN_PRB = "dqn_prb"
 DDQN_PRB = "ddqn_prb"
+DUELLING_DQN = "duelling_dqn"
+DUELLING_DDQN = "duelling_ddqn"
+DUELLING_DDQN_PRB = "duelling_ddqn_prb"
+DQN_NSTEP = "dqn_nstep"
+D3QN_PRB_NSTEP = "d3qn_prb_nstep"
 MCS = "mcts"
 PMCS = "pmcs"
 PUCT = "puct"
@@ -46,4 +56,12 @@ DQN_AGENTS = {
     DDQN: DDQNAgent,
     DQN_PRB: DQN_PRBAgent,
     DDQN_PRB: DDQN_PRBAgent,
+}
+
+DQN_VARIANT_AGENTS = {
+    DUELLING_DQN: DuellingDQNAgent,
+    DUELLING_DDQN: DuellingDDQNAgent,
+    DUELLING_DDQN_PRB: DuellingDDQN_PRBAgent,
+    DQN_NSTEP: DQN_NStep_Agent,
+    D3QN_PRB_NSTEP: D3QN_PRB_NStep,
 }

@@ -1,4 +1,4 @@
-"""Drop-in DQN agents (reference: rl_6_nimmt/agents/dqn.py:42-231,304-380,427).
+"""Drop-in DQN agents (reference: rl_6_nimmt/agents/dqn.py:42-231,264-436).
 
     DQNVanilla     Q(s,a) <- r + gamma * max_a' Q(s',a')
     DDQNAgent      Q(s,a) <- r + gamma * Q_target(s', argmax_a' Q(s',a')), the
@@ -8,6 +8,15 @@
                    priorities |Q(s,a) - target| written back before the
                    optimiser step
     DDQN_PRBAgent  both
+    DuellingDQNAgent, DuellingDDQNAgent, DuellingDDQN_PRBAgent
+                   the same three on DuellingDQNNet: Q = V + (A - mean A)
+    DQN_NStep_Agent
+                   rows of n_steps rewards: reward = sum_i r_{s+i} * gamma ** i,
+                   next_state n_steps on, target discount gamma ** n_steps;
+                   the last n_steps - 1 rows of an episode are flushed when it
+                   ends (fewer terms, done = True)
+    D3QN_PRB_NStep all of it: duelling, double, prioritised, n-step -- the
+                   agent the reference's author trains
 
 Host-side torch agents with the reference's constructor keywords and
 `forward` / `learn` contract, like the other drop-ins; the prioritised replay's
@@ -21,8 +30,15 @@ the reference, because seeded sessions depend on it:
     ones; `info["value"]` is -1 then;
   * every step is stored (with the *previous* step's reward, as GameSession
     passes it) and one minibatch is learned once `len(history) > minibatch`;
-    `learn` returns np.array([loss]).
-The duelling, noisy and n-step variants are not built.
+    `learn` returns np.array([loss]);
+  * the n-step reward is a Python float (float64): the target and the loss of
+    D3QN_PRB_NStep are float64.  DQN_NStep_Agent on the uniform replay keeps
+    the reference's failure too: MSELoss of a float32 q_eval and a float64
+    target raises in `backward` (DESIGN section 7);
+  * for n_steps > 1 the row that starts n_steps before the end points at the
+    terminal observation with done False, and the target uses gamma ** n_steps
+    for the truncated rows as well.
+The noisy variants (Noisy_DQN, Noisy_D3QN, Noisy_D3QN_PRB_NStep) are not built.
 """
 import math
 import random
@@ -31,7 +47,7 @@ import numpy as np
 import torch
 from torch import nn
 
-from ..utils.nets import MultiHeadedMLP
+from ..utils.nets import DuellingDQNNet, MultiHeadedMLP
 from ..utils.replay_buffer import History, PriorityReplayBuffer
 from .base import Agent
 
@@ -45,6 +61,11 @@ def eps_func_decay(episode):
 def _q_net(agent, hidden_sizes, activation):
     return MultiHeadedMLP(agent.state_length, hidden_sizes=hidden_sizes, head_sizes=(agent.num_actions,),
                           activation=activation, head_activations=(None,))
+
+
+def _duelling_net(agent, hidden_sizes, activation):
+    return DuellingDQNNet(agent.state_length, hidden_sizes=hidden_sizes, out_size=agent.num_actions,
+                          activation=activation)
 
 
 class DQNVanilla(Agent):
@@ -108,10 +129,21 @@ class DQNVanilla(Agent):
         self.eps = self.eps_func(num_episode)
         if self.summary_writer is not None and episode_end:
             self.summary_writer.add_scalar("debug/eps", self.eps, num_episode)
-        self.history.store(state=state, reward=reward, action=action, next_state=next_state, done=done)
-        if len(self.history) > self.minibatch:
+        self._store(state=state, reward=reward, action=action, next_state=next_state, done=done)
+        if len(self.history) > self._min_history_length():
             loss = self._learn(num_episode, episode_end)
+        if done:
+            self._finish_episode()
         return np.array([loss])
+
+    def _min_history_length(self):
+        return self.minibatch
+
+    def _store(self, **kwargs):
+        self.history.store(**kwargs)
+
+    def _finish_episode(self):
+        pass
 
     def _prep_minibatch(self, experiences):
         out = {}
@@ -196,4 +228,54 @@ class DQN_PRBAgent(DQNVanilla):
 
 
 class DDQN_PRBAgent(DQN_PRBAgent, DDQNAgent):
+    pass
+
+
+class DuellingDQNAgent(DQNVanilla):
+    """V and A heads on one latent net, Q = V + (A - mean_a A)"""
+
+    def _setup_networks(self, hidden_sizes, activation):
+        self.dqn_net_local = _duelling_net(self, hidden_sizes, activation)
+
+
+class DuellingDDQNAgent(DDQNAgent):
+    def _setup_networks(self, hidden_sizes, activation):
+        self.dqn_net_local = _duelling_net(self, hidden_sizes, activation)
+        self.dqn_net_target = _duelling_net(self, hidden_sizes, activation)  # left in train mode, as the reference's
+        self.soft_update(self.dqn_net_local, self.dqn_net_target, 1)
+
+
+class DQN_NStep_Agent(DQNVanilla):
+    def __init__(self, *args, **kwargs):
+        self.n_step_buffer = []
+        super().__init__(*args, **kwargs)
+
+    def _store(self, **kwargs):
+        self.n_step_buffer.append(kwargs)
+        if len(self.n_step_buffer) < self.n_steps:
+            return
+        R = sum([self.n_step_buffer[i][REWARD] * (self.gamma ** i) for i in range(self.n_steps)])
+        experience = self.n_step_buffer.pop(0)
+        experience[REWARD] = R
+        experience[NEXT_STATE] = kwargs[NEXT_STATE]
+        self.history.store(**experience)
+
+    def _finish_episode(self):
+        if len(self.n_step_buffer) == 0:
+            return
+        last = self.n_step_buffer[-1]
+        while len(self.n_step_buffer) > 0:
+            R = sum([self.n_step_buffer[i][REWARD] * (self.gamma ** i) for i in range(len(self.n_step_buffer))])
+            experience = self.n_step_buffer.pop(0)
+            experience[REWARD] = R
+            experience[NEXT_STATE] = last[NEXT_STATE]
+            experience[DONE] = True
+            self.history.store(**experience)
+
+
+class DuellingDDQN_PRBAgent(DQN_PRBAgent, DuellingDDQNAgent):
+    pass
+
+
+class D3QN_PRB_NStep(DQN_NStep_Agent, DuellingDDQN_PRBAgent):
     pass

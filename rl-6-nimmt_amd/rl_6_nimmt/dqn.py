@@ -1,6 +1,8 @@
 """Batched DQN family on one MI355X: the engine that seats DQNVanilla,
-DDQNAgent, DQN_PRBAgent and DDQN_PRBAgent (agents/dqn.py; reference
-agents/dqn.py:42-231,304-380,427) in the batched league.
+DDQNAgent, DQN_PRBAgent, DDQN_PRBAgent and their duelling and n-step
+variants (DuellingDQNAgent, DuellingDDQNAgent, DuellingDDQN_PRBAgent,
+DQN_NStep_Agent, D3QN_PRB_NStep; agents/dqn.py; reference
+agents/dqn.py:42-231,264-436) in the batched league.
 
 Every deciding seat of every game acts together.  Per decision batch:
     sn_dqn_obs     the raw _create_states rows (env.py:174-212), as int8 replay
@@ -9,9 +11,15 @@ Every deciding seat of every game acts together.  Per decision batch:
                    (a device copy in net_dtype, its input weight padded with a
                    zero column so the 48-wide rows go in unsliced)
     sn_dqn_select  epsilon-greedy over the hand (_action_selection), Philox
+A duelling net (utils.nets.DuellingDQNNet) runs as the FusedMLP of its `mlp`
+with the head rows ordered [A | V | pad]: one GEMM, and sn_dqn_select_duel
+forms Q = V + (A - mean A) per decision from that output in place.
 At the end of an episode sn_dqn_pack turns the staged observations, actions
 and rewards into 112-byte transition rows, stored in a DevicePER(capacity,
-112) -- for the uniform variants too: they draw slots and `gather`.
+112) -- for the uniform variants too: they draw slots and `gather`.  With
+n_steps > 1 sn_dqn_pack_nstep writes the n-step rows instead (the same T rows
+per decider; the return as f32 in the row's spare bytes), sn_dqn_unpack_nstep
+reads that return, and the targets discount by gamma ** n_steps.
 
 Learning (`learn`, once per round): `updates` minibatches of `minibatch`
 rows; per minibatch sample / gather -> sn_dqn_unpack -> fp32 forwards of
@@ -25,12 +33,16 @@ step's reward never reaches the agent; REINFORCE here keeps the same lag),
 done is set at the last step only, the length gate `len(replay) > minibatch`,
 the maximum over all 104 actions, unmasked, in the targets.
 Different by construction: exploration draws are Philox, not Python's
-`random` (parity unpinned, like the other engines' samplers), and a round
-trains on `updates` x `minibatch` rows, not 10 x 64 per game.
+`random` (parity unpinned, like the other engines' samplers), a round
+trains on `updates` x `minibatch` rows, not 10 x 64 per game, and the n-step
+targets and losses are fp32 (the reference's are float64: its n-step reward
+is a Python float).  Not built: the noisy variants, and replay inheritance
+for a cloned engine.
 
-`pack_rows_host`, `unpack_rows_host` and `bellman_target_host` are the torch
-models of the kernels (they run on any device); the tests hold the kernels
-to them.
+`pack_rows_host`, `unpack_rows_host`, `bellman_target_host`,
+`pack_rows_nstep_host`, `unpack_rows_nstep_host` and `duelling_q_host` are
+the torch models of the kernels (they run on any device); the tests hold the
+kernels to them.
 """
 import copy
 
@@ -46,6 +58,7 @@ OBS = 48  # 47 observation values + one zero pad
 NUM_ACTIONS = 104
 ROW_BYTES = 112
 OFF_STATE, OFF_NEXT_STATE, OFF_ACTION, OFF_DONE, OFF_HAND, OFF_REWARD = 0, 48, 96, 97, 98, 100
+OFF_TERMS, OFF_RETURN = 99, 104  # the n-step rows: rewards summed, the return as f32
 
 
 # ---------------------------------------------------------------- host models of the kernels
@@ -95,6 +108,70 @@ def bellman_target_host(q_next_local, q_next_target, reward, not_done, gamma):
         return reward + gamma * (best * not_done)
 
 
+def gamma_powers(gamma):
+    """gamma ** i for i < T_STEPS as CPython computes them (the reference's `self.gamma ** i`)"""
+    return [float(gamma) ** i for i in range(T_STEPS)]
+
+
+def nstep_returns_host(rewards_seen, n, gamma):
+    """float64 [T, D]: row s = sum([r[s + i] * gamma ** i for i in range(min(n, T - s))]), summed left to
+    right from 0 as Python's sum does (DQN_NStep_Agent._store / _finish_episode)"""
+    r = torch.as_tensor(rewards_seen).to(torch.float64)
+    T = r.shape[0]
+    gpow = gamma_powers(gamma)
+    out = torch.zeros_like(r)
+    for s in range(T):
+        acc = torch.zeros_like(r[s])
+        for i in range(min(int(n), T - s)):
+            acc = acc + r[s + i] * gpow[i]
+        out[s] = acc
+    return out
+
+
+def pack_rows_nstep_host(obs, actions, rewards_seen, n, gamma):
+    """sn_dqn_pack_nstep in torch: the rows DQN_NStep_Agent stores for an episode of T learn calls, in store
+    order.  Row s: state obs[s], next_state obs[min(s + n, T)], done = (s + n > T) or (n == 1 and s == T - 1),
+    byte 99 = m = min(n, T - s), bytes 100-103 r_s (int32), bytes 104-107 the n-step return
+    (nstep_returns_host) rounded once to float32.  T <= T_STEPS."""
+    obs = torch.as_tensor(obs).to(torch.int8)
+    actions, rewards_seen = torch.as_tensor(actions), torch.as_tensor(rewards_seen)
+    T, D = actions.shape
+    n = int(n)
+    assert 1 <= T <= T_STEPS and n >= 1
+    if obs.shape[-1] == OBS - 1:
+        obs = torch.cat((obs, torch.zeros_like(obs[..., :1])), dim=-1)
+    assert obs.shape == (T + 1, D, OBS)
+    dev = obs.device
+    start = torch.arange(T, device=dev)
+    nxt = torch.clamp(start + n, max=T)
+    rows = torch.zeros((T, D, ROW_BYTES), dtype=torch.uint8, device=dev)
+    rows[..., OFF_STATE: OFF_STATE + OBS] = obs[:-1].contiguous().view(torch.uint8)
+    rows[..., OFF_NEXT_STATE: OFF_NEXT_STATE + OBS] = obs[nxt].contiguous().view(torch.uint8)
+    rows[..., OFF_ACTION] = actions.to(dev).to(torch.uint8)
+    done = (start + n > T) | ((start == T - 1) & (n == 1))
+    rows[..., OFF_DONE] = done.to(torch.uint8)[:, None]
+    rows[..., OFF_HAND] = (obs[:-1, :, :10] >= 0).sum(dim=-1).to(torch.uint8)
+    rows[..., OFF_TERMS] = (nxt - start).to(torch.uint8)[:, None]
+    rew = rewards_seen.to(dev).to(torch.int32).contiguous()
+    rows[..., OFF_REWARD: OFF_REWARD + 4] = rew.view(torch.uint8).reshape(T, D, 4)
+    ret = nstep_returns_host(rew, n, gamma).to(torch.float32).contiguous()
+    rows[..., OFF_RETURN: OFF_RETURN + 4] = ret.view(torch.uint8).reshape(T, D, 4)
+    return rows.reshape(T * D, ROW_BYTES)
+
+
+def unpack_rows_nstep_host(rows):
+    """sn_dqn_unpack_nstep in torch: unpack_rows_host with reward = the float32 n-step return at byte 104"""
+    rows = torch.as_tensor(rows).reshape(-1, ROW_BYTES)
+    states, nxt, action, _, not_done = unpack_rows_host(rows)
+    reward = rows[:, OFF_RETURN: OFF_RETURN + 4].contiguous().view(torch.float32).reshape(-1)
+    return states, nxt, action, reward, not_done
+
+
+def duelling_q_host(V, A):
+    """DuellingDQNNet.forward's combination: V [n, 1], A [n, 104] -> Q [n, 104] (sn_dqn_select_duel's model)"""
+    return V + (A - A.mean(-1, keepdim=True))
+
+
 def league_capacity(history_length, seats):
     """replay rows of a league engine: the drop-in's history length and at least two expected rounds of
     transitions (`seats` expected seats of the agent per round, T_STEPS rows each), as a power of two"""
@@ -106,15 +183,23 @@ def league_capacity(history_length, seats):
 class BatchedDQN(BatchedPUCT):
     def __init__(self, env, q_net, target_net=None, prioritised=False, gamma=0.99, eps_func=None, minibatch=64,
                  updates=T_STEPS, retrain_interval=4, tau=1e-2, capacity=1 << 16, seed=0, net_dtype=torch.bfloat16,
-                 seats_mask=None, max_decisions=None):
+                 seats_mask=None, max_decisions=None, n_steps=1):
         """target_net given: the double-DQN target; prioritised: the PRB
-        variants (importance-weighted loss, priorities written back)"""
+        variants (importance-weighted loss, priorities written back); a
+        DuellingDQNNet as q_net (or target_net): the duelling variants;
+        n_steps > 1: the n-step rows and the discount gamma ** n_steps"""
         from .agents.dqn import eps_func_decay
+        from .utils.nets import DuellingDQNNet
 
         super().__init__(env, q_net, seed=seed, seats_mask=seats_mask, puct_root=False, net_dtype=net_dtype,
                          max_decisions=max_decisions)
         self.target_net, self.prioritised = target_net, bool(prioritised)
         self.gamma, self.tau = float(gamma), tau
+        self.n_steps = int(n_steps)
+        assert self.n_steps >= 1
+        self.duelling = isinstance(q_net, DuellingDQNNet)
+        assert target_net is None or isinstance(target_net, DuellingDQNNet) == self.duelling, \
+            "the local and the target net are of one kind"
         self.eps_func = eps_func_decay if eps_func is None else eps_func
         self.minibatch, self.updates, self.retrain_interval = int(minibatch), int(updates), int(retrain_interval)
         self.capacity = int(capacity)
@@ -132,12 +217,18 @@ class BatchedDQN(BatchedPUCT):
     # ------------------------------------------------------------ the Q net on the device
     def sync_net(self):
         """(re)build the device copy of the Q net in net_dtype; Linear/ReLU
-        layouts get the input weight padded to the 48-wide rows"""
+        layouts get the input weight padded to the 48-wide rows.  A duelling
+        net: the FusedMLP of its `mlp`, the head rows reordered [A | V | pad]
+        so that A starts every output row 16-byte aligned"""
         version = tuple(p._version for p in self.actor.parameters())
         if self._net is None or version != self._net_version:
             net = copy.deepcopy(self.actor).to(self.env.device, self.net_dtype)
             net.eval()
-            f = FusedMLP.of(net)
+            f = FusedMLP.of(net.mlp if self.duelling else net)
+            if self.duelling and f.layers is not None:
+                order = list(range(1, 1 + NUM_ACTIONS)) + [0] + list(range(1 + NUM_ACTIONS, f.head_w.shape[1]))
+                f.head_w, f.head_b = f.head_w[:, order].contiguous(), f.head_b[order].contiguous()
+                f.head_sizes = [NUM_ACTIONS, 1]
             if f.layers is not None:
                 w, b = f.layers[0]
                 if w.shape[1] == OBS - 1:
@@ -156,6 +247,19 @@ class BatchedDQN(BatchedPUCT):
         self.rows_evaluated += states.shape[0]
         out = out.float()
         return out if out.stride(1) == 1 else out.contiguous()
+
+    def _head_values(self, states):
+        """a duelling net's head output [D, stride] f32 with A in columns 0..103 and V in column 104: the
+        padded GEMM output as it is (stride 112), or [A | V] packed when the module runs unfused"""
+        net = self._net
+        with torch.no_grad():
+            if net.layers is not None:
+                out = net.head_out(states if net.layers[0][0].shape[1] == OBS else states[:, : OBS - 1])
+            else:
+                V, A = net(states[:, : OBS - 1])
+                out = torch.cat((A, V), dim=1)
+        self.rows_evaluated += states.shape[0]
+        return out.float().contiguous()
 
     def current_eps(self):
         return float(self.eps_func(self.episode)) if self.training else float(self.eps)
@@ -182,9 +286,16 @@ class BatchedDQN(BatchedPUCT):
         states = torch.empty((D, OBS), dtype=self.net_dtype, device=dev)
         nat.check(L.sn_dqn_obs(h, ctypes_ref(q), nat.ptr(obs_t), nat.ptr(states),
                                int(self.net_dtype == torch.bfloat16), st), "sn_dqn_obs")
-        qv = self._q_values(states)
-        nat.check(L.sn_dqn_select(h, ctypes_ref(q), nat.ptr(qv), qv.stride(0), self.eps_used, nat.ptr(self.actions),
-                                  nat.ptr(self.best_index), nat.ptr(self.value), st), "sn_dqn_select")
+        if self.duelling:
+            heads = self._head_values(states)
+            nat.check(L.sn_dqn_select_duel(h, ctypes_ref(q), nat.ptr(heads), heads.stride(0), NUM_ACTIONS, 0,
+                                           self.eps_used, nat.ptr(self.actions), nat.ptr(self.best_index),
+                                           nat.ptr(self.value), st), "sn_dqn_select_duel")
+        else:
+            qv = self._q_values(states)
+            nat.check(L.sn_dqn_select(h, ctypes_ref(q), nat.ptr(qv), qv.stride(0), self.eps_used,
+                                      nat.ptr(self.actions), nat.ptr(self.best_index), nat.ptr(self.value), st),
+                      "sn_dqn_select")
         if record:
             self._acts[self._t] = self.actions.view(-1)[self.decider_index()]
             self._t += 1
@@ -211,8 +322,14 @@ class BatchedDQN(BatchedPUCT):
             nat.check(L.sn_dqn_obs(h, ctypes_ref(q), nat.ptr(self._obs[T]), None, 0, st), "sn_dqn_obs")
             seen = self.rewards_seen(per_step, T).contiguous()
             rows = torch.empty((T * D, ROW_BYTES), dtype=torch.uint8, device=self.env.device)
-            nat.check(L.sn_dqn_pack(T, D, nat.ptr(self._obs), nat.ptr(self._acts), nat.ptr(seen), nat.ptr(rows), st),
-                      "sn_dqn_pack")
+            if self.n_steps > 1:
+                gpow = nat.SnDqnGpow()
+                gpow.v[:] = gamma_powers(self.gamma)
+                nat.check(L.sn_dqn_pack_nstep(T, D, self.n_steps, gpow, nat.ptr(self._obs), nat.ptr(self._acts),
+                                              nat.ptr(seen), nat.ptr(rows), st), "sn_dqn_pack_nstep")
+            else:
+                nat.check(L.sn_dqn_pack(T, D, nat.ptr(self._obs), nat.ptr(self._acts), nat.ptr(seen), nat.ptr(rows),
+                                        st), "sn_dqn_pack")
             for i in range(0, T * D, self.capacity):  # ring order = sequential stores
                 self.replay.store(rows[i: i + self.capacity])
         self._t = 0
@@ -249,18 +366,19 @@ class BatchedDQN(BatchedPUCT):
         action = torch.empty((n,), dtype=torch.int64, device=dev)
         reward = torch.empty((n,), dtype=torch.float32, device=dev)
         not_done = torch.empty((n,), dtype=torch.float32, device=dev)
-        nat.check(nat.lib().sn_dqn_unpack(n, nat.ptr(rows), nat.ptr(s), nat.ptr(s2), nat.ptr(action), nat.ptr(reward),
-                                          nat.ptr(not_done), self.env._stream()), "sn_dqn_unpack")
+        name = "sn_dqn_unpack_nstep" if self.n_steps > 1 else "sn_dqn_unpack"  # the f32 return, or the i32 reward
+        nat.check(getattr(nat.lib(), name)(n, nat.ptr(rows), nat.ptr(s), nat.ptr(s2), nat.ptr(action), nat.ptr(reward),
+                                           nat.ptr(not_done), self.env._stream()), name)
         return s, s2, action, reward, not_done
 
     def bellman_target(self, q_next_local, q_next_target, reward, not_done):
-        """sn_dqn_target on device tensors [n, stride >= 104] f32"""
+        """sn_dqn_target on device tensors [n, stride >= 104] f32, discounting by gamma ** n_steps"""
         assert q_next_local.stride(1) == 1 and (q_next_target is None or q_next_target.stride() == q_next_local.stride())
         n = int(q_next_local.shape[0])
         target = torch.empty((n,), dtype=torch.float32, device=q_next_local.device)
         nat.check(nat.lib().sn_dqn_target(n, nat.ptr(q_next_local), nat.ptr(q_next_target), q_next_local.stride(0),
-                                          nat.ptr(reward), nat.ptr(not_done), self.gamma, nat.ptr(target),
-                                          self.env._stream()), "sn_dqn_target")
+                                          nat.ptr(reward), nat.ptr(not_done), self.gamma ** self.n_steps,
+                                          nat.ptr(target), self.env._stream()), "sn_dqn_target")
         return target
 
     def loss_terms(self, batch):
@@ -324,7 +442,7 @@ class BatchedDQN(BatchedPUCT):
                    minibatch=max(int(agent.minibatch), slots), updates=T_STEPS,
                    retrain_interval=getattr(agent, "retrain_interval", 4), tau=getattr(agent, "tau", 1e-2),
                    capacity=league_capacity(agent.history.max_length, seats), seed=seed, net_dtype=net_dtype,
-                   max_decisions=slots)
+                   max_decisions=slots, n_steps=getattr(agent, "n_steps", 1))
 
     def begin_round(self, dec, agent, train):
         """training: eps_func(rounds finished); else the agent's own eps"""

@@ -104,10 +104,10 @@ def agent_kind(agent):
 
 def engine_kind(agent):
     """the batched engine that seats `agent` in a BatchedTournament: KIND_DQN
-    for the four DQN drop-ins (dqn.BatchedDQN), else agent_kind's answer"""
+    for the DQN drop-ins, the duelling and n-step variants included (dqn.BatchedDQN), else agent_kind's answer"""
     from .agents.dqn import DQNVanilla
 
-    if isinstance(agent, DQNVanilla):  # DDQNAgent, DQN_PRBAgent and DDQN_PRBAgent derive from it
+    if isinstance(agent, DQNVanilla):  # every other DQN agent derives from it
         return KIND_DQN
     return agent_kind(agent)
 

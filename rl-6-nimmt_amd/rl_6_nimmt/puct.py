@@ -116,13 +116,17 @@ class FusedMLP:
         self._fused = (c, w2p, head, w1s)
         return self._fused
 
-    def __call__(self, rows):
-        if self.layers is None:
-            return self.module(rows)
+    def head_out(self, rows):
+        """the padded head GEMM's output [rows, pad] as it is (fused layouts only)"""
         h = rows
         for w, b in self.layers:
             h = torch._addmm_activation(b, h, w.t())
-        out = torch.addmm(self.head_b, h, self.head_w)
+        return torch.addmm(self.head_b, h, self.head_w)
+
+    def __call__(self, rows):
+        if self.layers is None:
+            return self.module(rows)
+        out = self.head_out(rows)
         res, c = [], 0
         for n in self.head_sizes:
             res.append(out[:, c: c + n])

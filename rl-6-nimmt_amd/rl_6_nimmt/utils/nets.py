@@ -1,9 +1,12 @@
-"""Policy network of the MCS/PUCT agents (reference: rl_6_nimmt/utils/nets.py:100-132).
+"""Networks of the net agents (reference: rl_6_nimmt/utils/nets.py:100-144).
 
 `MultiHeadedMLP(input, hidden_sizes, head_sizes, activation, head_activations)`
-with the reference's module layout (`latent_net.<i>`, `head_nets.<h>.0`), so
-state_dicts are interchangeable with the reference's.  The noisy/duelling
-DQN variants are out of scope.
+with the reference's module layout (`latent_net.<i>`, `head_nets.<h>.0`), and
+`DuellingDQNNet(input, hidden_sizes, out_size, activation)`, which holds one as
+`mlp` with the heads (V: 1, A: out_size) and returns [V + (A - mean A)]
+(`mlp.latent_net.*`, `mlp.head_nets.0.0.*` = V, `mlp.head_nets.1.0.*` = A):
+state_dicts are interchangeable with the reference's.  The noisy layers are
+not built: `linear=` other than nn.Linear raises.
 """
 from torch import nn
 
@@ -27,3 +30,14 @@ class MultiHeadedMLP(nn.Module):
     def forward(self, inputs):
         latent = self.latent_net(inputs)
         return [head(latent) for head in self.head_nets]
+
+
+class DuellingDQNNet(nn.Module):
+    def __init__(self, input_size, hidden_sizes, out_size, activation, linear=nn.Linear, init_sigma=1.0):
+        super().__init__()
+        self.mlp = MultiHeadedMLP(input_size, hidden_sizes, (1, out_size), activation, (None, None), linear=linear,
+                                  init_sigma=init_sigma)
+
+    def forward(self, inputs):
+        V, A = self.mlp(inputs)
+        return [V + (A - A.mean(keepdim=True, dim=-1))]

@@ -13,6 +13,9 @@ Yardsticks:  obs     env.obs() + seat indexing + .float()
              unpack  slicing + .float() (dqn.unpack_rows_host)
              target  max / argmax + gather + mul + add (dqn.bellman_target_host)
              gather  index_select on a ring tensor
+             select_duel  dqn.duelling_q_host on the [A | V | pad] head output (stride 112), then
+                          sn_dqn_select on the materialised Q
+             pack_nstep   dqn.pack_rows_nstep_host (n = 3, gamma = 0.99)
 Algorithmic bytes per call: BYTES below.
 
 Usage:  python tools/dqn_prof.py [--reps 30] [--warmup 5] [--no-league] [--slots 65536] [--out dqn_prof.json]
@@ -34,7 +37,8 @@ D = GAMES * SEATS
 # what each call has to move: the device state it reads (3 hand + 8 board words per decision) or its inputs, and its outputs
 BYTES = {"obs": D * (44 + 48 + 192), "select": D * (12 + 10 * 4 + 12), "pack": T * D * (96 + 8 + 112),
          "unpack": MINIBATCH * (112 + 2 * 192 + 16), "target": MINIBATCH * (2 * 416 + 12),
-         "gather": MINIBATCH * (4 + 2 * 112)}
+         "gather": MINIBATCH * (4 + 2 * 112), "select_duel": D * (12 + 105 * 4 + 12),
+         "pack_nstep": T * D * (96 + 8 + 112)}
 
 
 def timed(fn):
@@ -48,7 +52,8 @@ def timed(fn):
 
 def kernel_legs():
     from rl_6_nimmt import _native as nat
-    from rl_6_nimmt.dqn import BatchedDQN, bellman_target_host, pack_rows_host, unpack_rows_host
+    from rl_6_nimmt.dqn import (BatchedDQN, bellman_target_host, duelling_q_host, gamma_powers, pack_rows_host,
+                                pack_rows_nstep_host, unpack_rows_host)
     from rl_6_nimmt.replay import DevicePER
     from rl_6_nimmt.utils.nets import MultiHeadedMLP
     from rl_6_nimmt.vec_env import VecSechsNimmtEnv
@@ -97,6 +102,17 @@ def kernel_legs():
         explore = u[0] <= 0.1
         return torch.where(explore, rnd, greedy), torch.where(explore, torch.full_like(best, -1.0), best)
 
+    heads = torch.randn((D, 112), device=dev, generator=g)  # [A | V | pad], as the engine's padded head GEMM leaves it
+
+    def select_duel_native():
+        nat.check(L.sn_dqn_select_duel(env._h, ref, nat.ptr(heads), 112, 104, 0, 0.1, nat.ptr(actions), nat.ptr(index),
+                                       nat.ptr(value), st), "sn_dqn_select_duel")
+
+    def select_duel_torch():
+        qd = duelling_q_host(heads[:, 104:105], heads[:, :104])
+        nat.check(L.sn_dqn_select(env._h, ref, nat.ptr(qd), qd.stride(0), 0.1, nat.ptr(actions), nat.ptr(index),
+                                  nat.ptr(value), st), "sn_dqn_select")
+
     ep_obs = torch.randint(0, 104, (T + 1, D, 48), dtype=torch.int8, device=dev, generator=g)
     ep_obs[..., 47] = 0
     ep_act = torch.randint(0, 104, (T, D), dtype=torch.int32, device=dev, generator=g)
@@ -106,6 +122,13 @@ def kernel_legs():
     def pack_native():
         nat.check(L.sn_dqn_pack(T, D, nat.ptr(ep_obs), nat.ptr(ep_act), nat.ptr(ep_rew), nat.ptr(ep_rows), st),
                   "sn_dqn_pack")
+
+    gpow = nat.SnDqnGpow()
+    gpow.v[:] = gamma_powers(0.99)
+
+    def pack_nstep_native():
+        nat.check(L.sn_dqn_pack_nstep(T, D, 3, gpow, nat.ptr(ep_obs), nat.ptr(ep_act), nat.ptr(ep_rew), nat.ptr(ep_rows),
+                                      st), "sn_dqn_pack_nstep")
 
     per = DevicePER(CAPACITY, 112, device=dev)
     ring = torch.randint(0, 256, (CAPACITY, 112), dtype=torch.uint8, device=dev, generator=g)
@@ -127,7 +150,10 @@ def kernel_legs():
             "unpack": (lambda: eng.unpack(batch), lambda: unpack_rows_host(batch)),
             "target": (lambda: eng.bellman_target(ql, qt, reward, not_done),
                        lambda: bellman_target_host(ql, qt, reward, not_done, eng.gamma)),
-            "gather": (lambda: per.gather(slots), lambda: ring.index_select(0, slots64))}, (env, eng, per)
+            "gather": (lambda: per.gather(slots), lambda: ring.index_select(0, slots64)),
+            "select_duel": (select_duel_native, select_duel_torch),
+            "pack_nstep": (pack_nstep_native, lambda: pack_rows_nstep_host(ep_obs, ep_act, ep_rew, 3, 0.99))}, \
+        (env, eng, per)
 
 
 def league_round(slots, rounds):

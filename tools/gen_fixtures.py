@@ -63,6 +63,16 @@ Fixture families (SURVEY.md §4 "What the build must add"):
                            the move, info["value"] and epsilon; the loss of
                            every learn(); the PER tree indices sampled;
                            initial and final weights
+  F17 dqn_variant_games.json  the F16 recipe for DuellingDQNAgent,
+      dqn_variant_weights.npz   DuellingDDQNAgent, DuellingDDQN_PRBAgent and
+                           D3QN_PRB_NStep(n_steps=3); for the n-step sessions
+                           also, for the first two games, every learn call's
+                           (state, reward, action, next_state, done) and the
+                           transitions the replay stored, in store order, with
+                           the reward as float64; the prioritised
+                           sessions also reject seeds whose importance
+                           weights hinge on a near-zero TD error
+                           (DQNVAR_MIN_LEAF)
 
 F15 / F16 pin the reference's *Python* semantics of the prioritised replay:
 with the stand-in numba.jit the sampler `_get_leaf_ids` runs as plain Python
@@ -1065,8 +1075,10 @@ DQN_GAP = 1e-3
 DQN_MARGIN = 1e-6
 
 
-def _dqn_session(cls_name, seed, eps_const):
-    """one seeded session, or None if the seed is too close to a tie"""
+def _dqn_session(cls_name, seed, eps_const, extra_kw=None, record_games=0, min_leaf=None):
+    """one seeded session, or None if the seed is too close to a tie.  record_games: also return the learn
+    calls and the replay's stored transitions of that many first games (a fifth element).  min_leaf: reject
+    the seed as well when a PER sample finds a smaller minimum leaf among the held items (DQNVAR_MIN_LEAF)"""
     import random
 
     import torch
@@ -1074,7 +1086,7 @@ def _dqn_session(cls_name, seed, eps_const):
     from rl_6_nimmt.play import GameSession
 
     torch.manual_seed(seed)
-    kw = dict(DQN_KW)
+    kw = dict(DQN_KW, **(extra_kw or {}))
     if eps_const is not None:
         kw["eps_func"] = lambda episode, _c=eps_const: _c
     ag = getattr(A, cls_name)(**kw)
@@ -1082,7 +1094,7 @@ def _dqn_session(cls_name, seed, eps_const):
     ag.train()
     init = {k: v.detach().numpy().astype(np.float32).copy() for k, v in ag.state_dict().items()}
     tr = {"steps": [], "losses": [], "per_idx": []}
-    worst = {"gap": float("inf"), "margin": float("inf")}
+    worst = {"gap": float("inf"), "margin": float("inf"), "leaf": float("inf")}
     sel, lrn = ag._action_selection, ag.learn
 
     def sel_rec(scores, **k):
@@ -1100,12 +1112,41 @@ def _dqn_session(cls_name, seed, eps_const):
         return loss
 
     ag._action_selection, ag.learn = sel_rec, lrn_rec
-    prb = "PRB" in cls_name
+    game = {"i": 0}
+    calls, stored = [[] for _ in range(record_games)], [[] for _ in range(record_games)]
+    if record_games:
+        def ints(x):
+            v = np.asarray(x, dtype=np.float64)
+            assert np.array_equal(v, np.round(v))
+            return [int(t) for t in v]
+
+        def transition(k):
+            return {"state": ints(k["state"]), "reward": float(k["reward"]), "action": int(k["action"]),
+                    "next_state": ints(k["next_state"]), "done": bool(k["done"])}
+
+        def lrn_calls(state, reward, action, done, next_state, *a, **k):
+            if game["i"] < record_games:
+                calls[game["i"]].append(transition(dict(state=state, reward=reward, action=action,
+                                                        next_state=next_state, done=done)))
+            return lrn_rec(state, reward, action, done, next_state, *a, **k)
+
+        hist_store = ag.history.store
+
+        def store_rec(**k):
+            if game["i"] < record_games:
+                assert isinstance(k["reward"], float)
+                stored[game["i"]].append(transition(k))
+            return hist_store(**k)
+
+        ag.learn, ag.history.store = lrn_calls, store_rec
+    prb = "PRB" in cls_name or "D3QN" in cls_name
     if prb:
         buf = ag.history
         smp = buf.sample
 
         def smp_rec(n):
+            first = len(buf.tree.tree) - buf.tree.capacity
+            worst["leaf"] = min(worst["leaf"], float(np.min(buf.tree.tree[first: first + buf.tree.num_items])))
             res, us, margin, _ = _recorded_sample(buf, n, smp)
             worst["margin"] = min(worst["margin"], margin)
             tr["per_idx"].append([int(x) for x in res[0]])
@@ -1115,22 +1156,30 @@ def _dqn_session(cls_name, seed, eps_const):
     np.random.seed(seed)
     random.seed(seed)
     sess = GameSession(*agents)
-    for _ in range(DQN_GAMES):
+    for gi in range(DQN_GAMES):
+        game["i"] = gi
         sess.play_game()
     if worst["gap"] < DQN_GAP or worst["margin"] < DQN_MARGIN:
         return None
+    if min_leaf is not None and worst["leaf"] < min_leaf:
+        return None
     final = {k: v.detach().numpy().astype(np.float32).copy() for k, v in ag.state_dict().items()}
-    rec = {"agent": cls_name, "seed": seed, "games": DQN_GAMES, "kwargs": DQN_KW, "eps_const": eps_const,
+    kw_json = dict(DQN_KW, **(extra_kw or {}))
+    rec = {"agent": cls_name, "seed": seed, "games": DQN_GAMES, "kwargs": kw_json, "eps_const": eps_const,
            "results": [[int(x) for x in r] for r in sess.results],            "greedy_steps": int(sum(1 for s in tr["steps"] if s[1] != -1)),
            "min_gap": None if worst["gap"] == float("inf") else worst["gap"]}
     if prb:
         rec.update(beta=float(ag.history.beta), total_priority=float(ag.history.tree.total_priority),
                    len=len(ag.history), min_margin=worst["margin"])
+        if min_leaf is not None:
+            rec.update(min_leaf=worst["leaf"])
     series = {"actions": np.array([s[0] for s in tr["steps"]], dtype=np.int64),
               "values": np.array([s[1] for s in tr["steps"]]), "eps": np.array([s[2] for s in tr["steps"]]),
               "losses": np.array(tr["losses"])}
     if prb:
         series["per_idx"] = np.array(tr["per_idx"], dtype=np.int64)
+    if record_games:
+        return rec, init, final, series, {"learn_calls": calls, "stored": stored}
     return rec, init, final, series
 
 
@@ -1167,6 +1216,65 @@ def gen_dqn(ref, out):
                    "sessions": sessions}, f)
 
 
+# ----------------------------------------------------------------------------
+# F17: the duelling and n-step DQN agents in training sessions
+# ----------------------------------------------------------------------------
+DQNVAR_CLASSES = [("DuellingDQNAgent", {}), ("DuellingDDQNAgent", {}), ("DuellingDDQN_PRBAgent", {}),
+                  ("D3QN_PRB_NStep", {"n_steps": 3})]
+DQNVAR_RECORD_GAMES = 2
+# A third rejection rule for the prioritised sessions.  Every importance weight of a sample is divided by the
+# largest one, (min leaf / total) ** -beta (replay_buffer.py:165,180), and a leaf is (|q - target| + 0.01) ** 0.6:
+# when the smallest held leaf comes from a TD error that nearly cancels, fp32 rounding on another CPU moves every
+# weight of the minibatch, and with them the loss, with d ln(loss) = beta * 0.6 * d|err| / (|err| + 0.01) and
+# beta < 0.45 in six games.  The floor of a leaf is 0.01 ** 0.6 = 0.063 and most seeds come within 0.07..0.13 of
+# it.  The sessions' losses are compared to a relative 1e-3; allowing the Q values (magnitudes up to 32 here) a
+# drift of 40 fp32 ulps = 1.5e-4 by the end of a session -- rounding amplified by sixty Adam steps -- asks for
+# |err| + 0.01 >= 0.45 * 0.6 * 1.5e-4 / 1e-3 = 0.041, i.e. leaf >= 0.041 ** 0.6 = 0.147; about one seed in six
+# qualifies.  (Seed 20 of DuellingDDQN_PRBAgent held a leaf of 0.077, from |err| = 0.004: the reference itself
+# moved its last four losses by 7e-5 under a 1e-6 change of one initial weight.)
+DQNVAR_MIN_LEAF = 0.15
+
+
+def gen_dqnvar(ref, out):
+    sessions, arrays = [], {}
+    for ci, (cls_name, extra) in enumerate(DQNVAR_CLASSES):
+        nstep = "n_steps" in extra
+        for eps_const in (None, 0.3):
+            seed = 10 * ci + (5 if eps_const else 0)
+            while True:
+                got = _dqn_session(cls_name, seed, eps_const, extra_kw=extra,
+                                   record_games=DQNVAR_RECORD_GAMES if nstep else 0,
+                                   min_leaf=DQNVAR_MIN_LEAF if "PRB" in cls_name else None)
+                if got is not None:
+                    break
+                seed += 100  # rejected, by the F16 rules or DQNVAR_MIN_LEAF
+            rec, init, final, series = got[:4]
+            if nstep:
+                rec.update(got[4])
+            si = len(sessions)
+            for k, v in series.items():
+                arrays[f"s{si}_{k}"] = v
+            for k, v in init.items():
+                if k.startswith("dqn_net_target."):  # the local net's copy (soft_update with tau = 1): not stored
+                    assert np.array_equal(v, init[k.replace("dqn_net_target.", "dqn_net_local.", 1)])
+                    continue
+                arrays[f"s{si}_init_{k}"] = v
+            for k, v in final.items():
+                arrays[f"s{si}_final_{k}"] = v
+            sessions.append(rec)
+    np.savez_compressed(os.path.join(out, "dqn_variant_weights.npz"), **arrays)
+    with open(os.path.join(out, "dqn_variant_games.json"), "w") as f:
+        json.dump({"protocol": "dqn_games.json's protocol and rejection rules for DuellingDQNAgent, DuellingDDQNAgent, "
+                               "DuellingDDQN_PRBAgent and D3QN_PRB_NStep (kwargs holds n_steps); arrays in "
+                               "dqn_variant_weights.npz under the same names (the prioritised sessions also reject a seed whose smallest held leaf at "
+                               "any sample is below 0.15 (min_leaf): an ill-conditioned weight normalisation), without s<i>_init_dqn_net_target.* (equal to "
+                               "s<i>_init_dqn_net_local.*).  The n-step sessions also hold, for the "
+                               "first two games: learn_calls[game] = the (state, reward, action, next_state, done) of "
+                               "every learn() call, stored[game] = the transitions the replay's store() received, in "
+                               "store order, the reward a float64 (Python float)",
+                   "sessions": sessions}, f)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests", "golden"))
@@ -1190,6 +1298,7 @@ def main():
         ("evolve", gen_evolve),
         ("per", gen_per),
         ("dqn", gen_dqn),
+        ("dqnvar", gen_dqnvar),
     ]
     for name, fn in steps:
         if args.only and name not in args.only.split(","):
