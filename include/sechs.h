@@ -219,6 +219,17 @@ sn_status sn_philox_counter(sn_env* env, int64_t game, uint64_t* counter_host);
                          ring-reading paths keep one launch per chunk (their
                          launches are bounded by the ring window).  Same
                          outputs, same exported numpy states.
+     SN_OPT_DEC_WALK     1 (default): k_decode reads the DrunkHamster draws of a
+                         step straight from its LDS window by stream position,
+                         16 words per look, as it reads the shuffle targets;
+                         a step with fewer than 16 live window bytes left (a
+                         short lead, an overrun) goes through the byte buffer.
+                         0: every step's draws go through the byte buffer (the
+                         form before round 10).  Read at every k_decode
+                         dispatch.  Same records word for word, so the same
+                         outputs and exported numpy states; the environment
+                         variable SECHS_DEC_WALK overrides the default at
+                         sn_create.
    A pipelined (numpy-compat) rollout records its ordering event on the
    caller's stream before it returns; every later call waits on that event
    (also on the same stream), so the caller may destroy the stream after
@@ -226,7 +237,7 @@ sn_status sn_philox_counter(sn_env* env, int64_t game, uint64_t* counter_host);
 enum { SN_OPT_RING_WORDS = 1, SN_OPT_CHUNK_STEPS = 2, SN_OPT_PIPELINE = 3, SN_OPT_TIMING = 4, SN_OPT_PIPE_GPW = 5,
        SN_OPT_PIPE_LEAD = 6, SN_OPT_PLAY_SPLIT = 7, SN_OPT_PLAY_QUAD = 8, SN_OPT_TWIST_ROUND = 9,
        SN_OPT_TWIST_EVERY = 10, SN_OPT_PIPE_FUSED = 11, SN_OPT_TWIST_SKIP = 12, SN_OPT_PIPE_DEC = 13,
-       SN_OPT_TWIST_DEPTH = 14, SN_OPT_PLAY_GROUP = 15 };
+       SN_OPT_TWIST_DEPTH = 14, SN_OPT_PLAY_GROUP = 15, SN_OPT_DEC_WALK = 16 };
 sn_status sn_set_option(sn_env* env, int option, int value);
 /* pipelined rollouts whose draws ran past the twisted words (must be 0; a
    nonzero count means those games' draws are wrong) [sync].  The count is
@@ -257,7 +268,7 @@ sn_status sn_debug_phases(uint64_t* out, int n);
    out[7] = waves; read and cleared.  SN_EUNSUPPORTED in the product library. */
 sn_status sn_debug_puct_phases(uint64_t* out, int n);
 /* pipeline words to the host (tests, diagnostics) [sync]: what 0 = pabsc[slot]
-   (consumer positions, slot kPipeSlots = the decoder's; B words), 1 =
+   (consumer positions, slots 8 and 9 = the decoder's two; B words), 1 =
    ptend[slot] (B words), 2 = decode-ahead record slot (kDecQuads x B 16-B
    pieces, piece-major).  No pipeline state is changed. */
 sn_status sn_debug_pipe_words(sn_env* env, int what, int slot, uint32_t* out);

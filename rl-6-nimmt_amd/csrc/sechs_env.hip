@@ -1083,7 +1083,34 @@ constexpr int kDecBlock = 64;  // one wave per workgroup: packs beside the play 
 constexpr int kDecLane = kPipeSlot;
 static_assert(kDecLane % 8 == 0 && (kDecLane / 8) % 2 == 1 && kDecLane >= 112 + 108, "decoder LDS lane");
 
+// A step of the WALK form whose window is too short (walk_draws returned false): rng_draws on an
+// empty byte buffer from stream offset t, which reads on past the window byte by byte, stops at the
+// twisted end and counts an overrun, as in the other form.  The buffer lives in this branch only, so
+// it does not count in the decoder's allocation: 85 VGPRs and no scratch at N = 4, the other form
+// 90 (out of line, as pipe_slow is, the call cost 103 VGPRs and a 16-byte frame).  Returns the
+// offset after the step and the draws, a nibble each.
+struct DecSlow {
+    uint32_t t, idx;
+};
+
 template <int N>
+static __device__ __forceinline__ DecSlow dec_draws_slow(RingPipe rng, uint32_t t, uint32_t max) {
+    ByteBuf buf;
+    buf.clear();
+    rng.take = t;
+    uint32_t idx[N];
+    rng_draws<N>(rng, buf, max, idx);
+    DecSlow r;
+    r.t = rng.take - buf.cnt;  // buffered bytes are re-read from the window, as shuffle_targets does
+    r.idx = 0u;
+#pragma unroll
+    for (int p = 0; p < N; p++) r.idx |= idx[p] << (4 * p);
+    return r;
+}
+
+// WALK (SN_OPT_DEC_WALK, the default): the draws too are read by window position (walk_draws); a
+// step the window is too short for goes through the byte buffer as in the other form.
+template <int N, bool WALK>
 __global__ __launch_bounds__(kDecBlock) void k_decode(DevState s, DecArgs d) {
     __shared__ __attribute__((aligned(16))) uint8_t lds[kDecBlock * kDecLane];
     const int lane = threadIdx.x & 63;
@@ -1105,22 +1132,37 @@ __global__ __launch_bounds__(kDecBlock) void k_decode(DevState s, DecArgs d) {
         const uint32_t start = pos;
         uint32_t off[5] = {0u, 0u, 0u, 0u, 0u}, dr[5] = {0u, 0u, 0u, 0u, 0u};
         bool big = false;
+        uint32_t wt = 0u;  // WALK: the next unconsumed byte of the window (the buffer stays empty)
 #pragma unroll
         for (int t = 0; t < kHand - 1; t++) {  // steps 0..8: hand size n = 10 - t, draws random_interval(n - 1)
             if (t >= phi) {
                 uint32_t idx[N];
-                rng_draws<N>(rng, buf, (uint32_t)(kHand - 1 - t), idx);
+                if constexpr (WALK) {
+                    if (!walk_draws<N>(rng, wt, (uint32_t)(kHand - 1 - t), idx)) {
+                        // max as a run-time value here: with it constant, the nine copies' 64-bit masks are
+                        // hoisted out of the episode loop and sit in VGPRs beside the window load
+                        uint32_t mx = (uint32_t)(kHand - 1 - t);
+                        asm volatile("" : "+v"(mx));
+                        const DecSlow r = dec_draws_slow<N>(rng, wt, mx);
+                        wt = r.t;
+#pragma unroll
+                        for (int p = 0; p < N; p++) idx[p] = (r.idx >> (4 * p)) & 15u;
+                    }
+                } else {
+                    rng_draws<N>(rng, buf, (uint32_t)(kHand - 1 - t), idx);
+                }
                 uint32_t v = 0u;
 #pragma unroll
                 for (int p = 0; p < N; p++) v |= idx[p] << (4 * p);
                 dr[t >> 1] |= v << (16 * (t & 1));
-                const uint32_t o = rng.consumed(buf) - start;
+                const uint32_t o = WALK ? wt : rng.consumed(buf) - start;  // the window starts at `start`
                 big = big || o > 0xFFFFu;
                 off[t >> 1] |= (o & 0xFFFFu) << (16 * (t & 1));
             }
         }
         pq.mark(PR_DRAWS);
         // step 9 plays each seat's last card (no draw), then the auto-reset deal
+        if constexpr (WALK) rng.take = wt;
         shuffle_targets(rng, buf, jslot, s.C, kDecLane - 1);  // the window's own form (by position), dummy past it
         pos = rng.consumed(buf);
         pq.mark(PR_TARGETS);
@@ -1770,6 +1812,11 @@ sn_status sn_create(sn_env** out, int device, int64_t num_games, int num_players
         const char* pg = getenv("SECHS_PLAY_GROUP");  // default override (A/B runs of whole legs)
         if (pg && (pg[0] == '0' || pg[0] == '1') && !pg[1]) e->opt.play_group = pg[0] - '0';
     }
+    e->opt.dec_walk = 1;  // k_decode's draws by window position
+    {
+        const char* dw = getenv("SECHS_DEC_WALK");  // default override (A/B runs of whole legs)
+        if (dw && (dw[0] == '0' || dw[0] == '1') && !dw[1]) e->opt.dec_walk = dw[0] - '0';
+    }
     e->opt.pipe_dec = 1;  // decode-ahead where it applies: 0.0776 -> 0.069 ms per step same box
     {
         const char* pd = getenv("SECHS_PIPE_DEC");  // default override (A/B runs of whole legs)
@@ -1931,6 +1978,11 @@ sn_status sn_set_option(sn_env* e, int option, int value) {
         case SN_OPT_PLAY_GROUP:  // the launch form only: the pipeline's bookkeeping is in chunks either way, no restart
             if (value < 0 || value > 1) return fail(SN_EINVAL, "play group must be 0 or 1");
             e->opt.play_group = value;
+            return SN_OK;
+        case SN_OPT_DEC_WALK:  // the form of k_decode only, read at every dispatch (dec_launch): the same records either
+                               // way, so nothing past the pipeline sync every option change begins with (above)
+            if (value < 0 || value > 1) return fail(SN_EINVAL, "dec walk must be 0 or 1");
+            e->opt.dec_walk = value;
             return SN_OK;
         case SN_OPT_TWIST_SKIP:
             if (value < 0 || value > 1) return fail(SN_EINVAL, "twist skip must be 0 or 1");
@@ -2193,7 +2245,10 @@ static sn_status dec_launch(sn_env* e, int64_t e0, int ne, int phi0, int tpar, i
     const DecArgs d{dec_record(e0), ne, phi0, tpar, cin, cout};
     const dim3 grid((unsigned)((s.B + kDecBlock - 1) / kDecBlock));
     SN_DISPATCH_N(s.N, {
-        if constexpr (NN <= kSplitMaxPlayers) hipLaunchKernelGGL((k_decode<NN>), grid, dim3(kDecBlock), 0, st, s, d);
+        if constexpr (NN <= kSplitMaxPlayers) {
+            if (e->opt.dec_walk) hipLaunchKernelGGL((k_decode<NN, true>), grid, dim3(kDecBlock), 0, st, s, d);
+            else hipLaunchKernelGGL((k_decode<NN, false>), grid, dim3(kDecBlock), 0, st, s, d);
+        }
     });
     HIP_TRY(hipGetLastError());
     return SN_OK;
@@ -2803,7 +2858,7 @@ sn_status sn_debug_pipe_words(sn_env* e, int what, int slot, uint32_t* out) {
     const int64_t B = e->s.B;
     const void* src = nullptr;
     size_t bytes = 0;
-    if (what == 0 && slot >= 0 && slot <= kPipeSlots) src = e->s.pabsc + (int64_t)slot * B, bytes = 4 * B;
+    if (what == 0 && slot >= 0 && slot < kPipeSlots + 2) src = e->s.pabsc + (int64_t)slot * B, bytes = 4 * B;
     else if (what == 1 && slot >= 0 && slot < 2) src = e->s.ptend + (int64_t)slot * B, bytes = 4 * B;
     else if (what == 2 && slot >= 0 && slot < kDecRecords && e->s.drec)
         src = e->s.drec + (int64_t)slot * kDecQuads * B, bytes = sizeof(u32x4) * kDecQuads * B;

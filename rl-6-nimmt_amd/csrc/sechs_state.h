@@ -451,6 +451,71 @@ __device__ __forceinline__ void shuffle_targets(RingPipe& rng, ByteBuf& buf, uin
 // bytes of a lane's LDS window for RingPipe (chunk-aligned copy + 8 for the funnel's second read)
 constexpr int kPipeSlot = ((kPipeWin + 15 + 15) / 16) * 16 + 8;
 
+// rng_draws<K> on the pipelined ring by window position (k_decode, SN_OPT_DEC_WALK): t is the next
+// unconsumed byte of the window as in shuffle_targets, the byte buffer is not touched.  Every peek
+// needs 16 live window bytes from t on; the last aligned read then ends at most at byte
+// 15 + kPipeWin + 8 of the lane's slot (five dwords from the one t lies in).  Returns false with t
+// and the stream untouched when a peek finds fewer (a short window: start-up, a shortened lead, an
+// overrun): the caller runs the whole step through rng_draws, which knows the window's end, `tend`
+// and the overrun count.  Same words, same draws as rng_draws.
+static_assert(15 + kPipeWin + 8 <= kPipeSlot, "walk_draws reads 16 window bytes as five aligned dwords");
+template <int K>
+__device__ __forceinline__ bool walk_draws(const RingPipe& rng, uint32_t& t, uint32_t max, uint32_t (&out)[K]) {
+    static_assert(K >= 1 && K <= 4, "the accept-all form reads the draws from one dword");
+#pragma unroll
+    for (int k = 0; k < K; k++) out[k] = 0u;
+    if (max == 0u) return true;
+    uint32_t tt = t;
+    if (tt + 16u > rng.win) return false;
+    const uint32_t mask = 0xFFFFFFFFu >> __builtin_clz(max);
+    if (max == mask) {  // every word is accepted (max 7, 3, 1): the next K bytes are the draws
+        const uint32_t p = rng.off + tt, a4 = p & ~3u;
+        const uint64_t w = (uint64_t) * (const uint32_t*)(rng.slot + a4) | ((uint64_t) * (const uint32_t*)(rng.slot + a4 + 4u) << 32);
+        const uint32_t x = (uint32_t)(w >> (8u * (p & 3u)));
+#pragma unroll
+        for (int k = 0; k < K; k++) out[k] = (x >> (8 * k)) & mask;
+        t = tt + (uint32_t)K;
+        return true;
+    }
+    // 32-bit arithmetic throughout (the VALU runs 64-bit shifts and adds as instruction pairs): five
+    // aligned dwords funnelled to the 16 bytes, a SWAR compare per dword, its four 0x80 flags
+    // gathered into a nibble by two shift-and-or steps, so the accepted words of the look are the
+    // set bits of one 16-bit mask
+    const uint32_t mb = 0x01010101u * mask, cmp = 0x01010101u * (max | 0x80u);
+    uint32_t got = 0u;
+    while (true) {  // a second pass only where 16 words hold fewer than K accepted ones
+        const uint32_t p = rng.off + tt, sh = 8u * (p & 3u);
+        const uint32_t* q = (const uint32_t*)(rng.slot + (p & ~3u));
+        uint32_t d[5], acc = 0u;
+#pragma unroll
+        for (int j = 0; j < 5; j++) d[j] = q[j];
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            const uint32_t x = (uint32_t)((((uint64_t)d[j + 1] << 32) | d[j]) >> sh) & mb;
+            const uint32_t f = (cmp - x) & 0x80808080u;  // byte k of x <= max: bit 8k + 7 (swar_le_mask)
+            const uint32_t g = (f >> 7) | (f >> 14);     // bytes 0, 1 -> bits 0, 1; bytes 2, 3 -> bits 16, 17
+            acc |= ((g | (g >> 14)) & 15u) << (4 * j);
+        }
+        uint32_t last = 0u;
+#pragma unroll
+        for (int k = 0; k < K; k++) {  // draw k is taken in this pass iff the passes before left it open
+            const bool has = (uint32_t)k >= got && acc != 0u;
+            const uint32_t pos = (uint32_t)__builtin_ctz(acc | 0x10000u);  // 16: none left, a byte of the slot still
+            const uint32_t v = (uint32_t)rng.slot[p + pos] & mask;
+            out[k] = has ? v : out[k];
+            acc = has ? (acc & (acc - 1u)) : acc;
+            last = has ? pos : last;
+            got += has ? 1u : 0u;
+        }
+        if (got == (uint32_t)K) {
+            t = tt + last + 1u;  // through the K-th accepted word
+            return true;
+        }
+        tt += 16u;
+        if (tt + 16u > rng.win) return false;
+    }
+}
+
 // bytes of a lane's LDS ring slot (+8: odd 8-B stride, conflict-free ds_read_b64 rows)
 __host__ __device__ constexpr int ring_lds_stride(int ring_w) { return ring_w + 8; }
 
@@ -910,6 +975,7 @@ struct sn_env {
         int pipe_lead;    // SN_OPT_PIPE_LEAD: words k_mt_ahead keeps twisted ahead (kPipeLead; tests lower it)
         int pipe_dec;     // SN_OPT_PIPE_DEC: decode-ahead (k_decode + k_play<RNG_NUMPY_DEC>) where it applies
         int play_group;   // SN_OPT_PLAY_GROUP: decode-ahead plays a call's chunks of one twist group in one k_play launch
+        int dec_walk;     // SN_OPT_DEC_WALK: k_decode reads its draws by window position (1) or through the byte buffer (0)
         int pipe_serial;  // SECHS_PIPE_SERIAL=1 (diagnostics): each twist waits for the play launch before it (no overlap)
         int play_split;   // SN_OPT_PLAY_SPLIT: role-split k_play for lockstep DrunkHamster rollouts
         int twist_every;  // SN_OPT_TWIST_EVERY: a k_mt_ahead beside every K-th play launch (K = 1 .. 5)

@@ -187,13 +187,14 @@ class VecSechsNimmtEnv:
     # ------------------------------------------------------------ numpy RNG bridge
     def set_option(self, ring_words=None, chunk_steps=None, pipeline=None, pipe_gpw=None, pipe_lead=None,
                    play_split=None, twist_round=None, twist_every=None, twist_skip=None, pipe_dec=None,
-                   twist_depth=None, play_group=None):
+                   twist_depth=None, play_group=None, walk_draws=None):
         """rollout tuning (include/sechs.h SN_OPT_*; all numpy-compat only except play_split,
         the role-split kernel of philox handles; twist_round: whole-round MT twists in
         k_mt_ahead; twist_every: one twist-ahead launch per K = 1 .. 5 play launches; twist_depth:
         0 .. 3 extra rounds a refilling game twists past the lead, chained in LDS; pipe_dec:
         decode-ahead, k_decode + k_play from the records; play_group: decode-ahead plays a call's
-        chunks of one twist group in one k_play launch); results never
+        chunks of one twist group in one k_play launch; walk_draws: k_decode reads its draws by
+        window position (1) or through the byte buffer (0)); results never
         depend on it (except the test knobs pipe_lead < 600 and twist_skip = 1, which make
         overruns -- PipeOverrunError -- likely / certain)"""
         if pipe_lead is not None:
@@ -210,6 +211,8 @@ class VecSechsNimmtEnv:
             nat.check(nat.lib().sn_set_option(self._h, nat.SN_OPT_TWIST_DEPTH, int(twist_depth)), "sn_set_option")
         if play_group is not None:
             nat.check(nat.lib().sn_set_option(self._h, nat.SN_OPT_PLAY_GROUP, int(play_group)), "sn_set_option")
+        if walk_draws is not None:
+            nat.check(nat.lib().sn_set_option(self._h, nat.SN_OPT_DEC_WALK, int(walk_draws)), "sn_set_option")
         if pipe_dec is not None:
             nat.check(nat.lib().sn_set_option(self._h, nat.SN_OPT_PIPE_DEC, int(pipe_dec)), "sn_set_option")
         if twist_skip is not None:
