@@ -432,7 +432,20 @@ sn_status sn_mcs_decide_exact(int device, int64_t num_decisions, int num_players
                      root / policy samples elsewhere, env step, backup at the end)
      sn_puct_choose     actions [B][N] int32 of the deciding seats = best mean
    Buffers (device, caller-owned): rollouts [D][48] i32, stats [D][24] i32,
-   hist [D][172] i32, root_probs [D][10] f32. */
+   hist [D][172] i32, root_probs [D][10] f32.
+   The five search buffers (avail, rollouts, stats, hist, root_probs) are
+   required by exactly the calls whose kernels read or write them, and those
+   calls return SN_EINVAL, naming the field and launching nothing, when one
+   they need is NULL:
+     sn_puct_init        stats, hist, root_probs
+     sn_puct_deal        avail, rollouts        sn_puct_deal_batch  avail
+     sn_puct_rows        rollouts               sn_puct_mlp_seats   rollouts
+     sn_puct_step        rollouts, stats, hist, root_probs
+     sn_puct_rollouts    stats, hist, root_probs
+     sn_puct_choose      stats (n > 1)
+   They may all be NULL for sn_puct_root_rows, sn_pcv_choose,
+   sn_policy_sample and sn_dqn_* (those kernels take only the deciding seats,
+   n, seed and step from this struct). */
 typedef struct {
     uint32_t seats_mask;   /* deciding seats (bit p = seat p) */
     int n;                 /* hand size at the root (all games in lockstep) */

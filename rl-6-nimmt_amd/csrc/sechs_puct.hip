@@ -1622,8 +1622,28 @@ __global__ void k_puct_score(int64_t D, int n_max, const int32_t* n, const int32
 // ============================================================================
 // C ABI
 // ============================================================================
-static sn_status puct_args(sn_env* e, const sn_puct* q, PuctArgs& a) {
+// the search buffers of sn_puct an entry point's kernels dereference (include/sechs.h, at sn_puct):
+// checked on the host before anything is launched
+enum : unsigned { kNeedAvail = 1, kNeedRo = 2, kNeedStats = 4, kNeedHist = 8, kNeedProbs = 16 };
+static sn_status puct_need(const sn_puct* q, unsigned need) {
+    const struct {
+        unsigned bit;
+        const void* p;
+        const char* name;
+    } fields[] = {{kNeedAvail, q->avail, "avail"},
+                  {kNeedRo, q->rollouts, "rollouts"},
+                  {kNeedStats, q->stats, "stats"},
+                  {kNeedHist, q->hist, "hist"},
+                  {kNeedProbs, q->root_probs, "root_probs"}};
+    for (const auto& f : fields)
+        if ((need & f.bit) && !f.p)
+            return set_error(SN_EINVAL, std::string("sn_puct.") + f.name + " is NULL: this call reads or writes it");
+    return SN_OK;
+}
+
+static sn_status puct_args(sn_env* e, const sn_puct* q, PuctArgs& a, unsigned need = 0) {
     if (!e || !q) return set_error(SN_EINVAL, "NULL argument");
+    if (sn_status st = puct_need(q, need); st != SN_OK) return st;
     if (q->n < 1 || q->n > kHand) return set_error(SN_EINVAL, "hand size out of range");
     a.N = e->s.N;
     a.lgs = e->s.lg_K ? e->s.lgs : nullptr;
@@ -1673,7 +1693,7 @@ sn_status sn_puct_root_rows(sn_env* e, const sn_puct* q, void* rows, int bf16, v
 
 sn_status sn_puct_init(sn_env* e, const sn_puct* q, const float* root_logits, void* stream) {
     PuctArgs a{};
-    sn_status st = puct_args(e, q, a);
+    sn_status st = puct_args(e, q, a, kNeedStats | kNeedHist | kNeedProbs);
     if (st != SN_OK) return st;
     hipLaunchKernelGGL(k_puct_init, dim3(grid_for(a.D)), dim3(kBlock), 0, (hipStream_t)stream, a, root_logits);
     HIP_TRY(hipGetLastError());
@@ -1682,7 +1702,7 @@ sn_status sn_puct_init(sn_env* e, const sn_puct* q, const float* root_logits, vo
 
 sn_status sn_puct_deal(sn_env* e, const sn_puct* q, void* stream) {
     PuctArgs a{};
-    sn_status st = puct_args(e, q, a);
+    sn_status st = puct_args(e, q, a, kNeedAvail | kNeedRo);
     if (st != SN_OK) return st;
     hipStream_t s = (hipStream_t)stream;
     SN_DISPATCH_N(e->s.N, hipLaunchKernelGGL((k_puct_deal<NN>), dim3(grid_for(a.D)), dim3(kBlock), 0, s, e->s, a));
@@ -1692,7 +1712,7 @@ sn_status sn_puct_deal(sn_env* e, const sn_puct* q, void* stream) {
 
 sn_status sn_puct_deal_batch(sn_env* e, const sn_puct* q, int r0, int nr, void* ro_out, void* stream) {
     PuctArgs a{};
-    sn_status st = puct_args(e, q, a);
+    sn_status st = puct_args(e, q, a, kNeedAvail);
     if (st != SN_OK) return st;
     if (r0 < 0 || nr < 1 || !ro_out) return set_error(SN_EINVAL, "need r0 >= 0, nr >= 1 and an output buffer");
     hipStream_t s = (hipStream_t)stream;
@@ -1705,7 +1725,7 @@ sn_status sn_puct_deal_batch(sn_env* e, const sn_puct* q, int r0, int nr, void* 
 
 sn_status sn_puct_rows(sn_env* e, const sn_puct* q, int n_cur, void* rows, int bf16, void* stream) {
     PuctArgs a{};
-    sn_status st = puct_args(e, q, a);
+    sn_status st = puct_args(e, q, a, kNeedRo);
     if (st != SN_OK) return st;
     if (n_cur < 1 || n_cur > a.n) return set_error(SN_EINVAL, "n_cur out of range");
     const int64_t total = a.D * e->s.N * n_cur;
@@ -1721,7 +1741,7 @@ sn_status sn_puct_rows(sn_env* e, const sn_puct* q, int n_cur, void* rows, int b
 
 sn_status sn_puct_step(sn_env* e, const sn_puct* q, const float* logits, int t, int n_cur, void* stream) {
     PuctArgs a{};
-    sn_status st = puct_args(e, q, a);
+    sn_status st = puct_args(e, q, a, kNeedRo | kNeedStats | kNeedHist | kNeedProbs);
     if (st != SN_OK) return st;
     if (n_cur < 1 || n_cur > a.n || t < 0 || t + n_cur != a.n) return set_error(SN_EINVAL, "t / n_cur inconsistent");
     hipStream_t s = (hipStream_t)stream;
@@ -1769,7 +1789,7 @@ sn_status sn_puct_step(sn_env* e, const sn_puct* q, const float* logits, int t, 
 sn_status sn_puct_mlp_seats(sn_env* e, const sn_puct* q, int n_cur, const void* w1s, const float* w1c, const void* w2,
                             const float* head, float* logits, void* stream) {
     PuctArgs a{};
-    sn_status st = puct_args(e, q, a);
+    sn_status st = puct_args(e, q, a, kNeedRo);
     if (st != SN_OK) return st;
     if (n_cur < 1 || n_cur > a.n) return set_error(SN_EINVAL, "n_cur out of range");
     if (!w1s || !w1c || !w2 || !head || !logits) return set_error(SN_EINVAL, "NULL argument");
@@ -1789,7 +1809,7 @@ sn_status sn_puct_mlp_seats(sn_env* e, const sn_puct* q, int n_cur, const void* 
 sn_status sn_puct_rollouts(sn_env* e, const sn_puct* q, int r0, int nr, void* ro_base, const void* w1s, const float* w1c,
                            const void* w2, const float* head, void* stream) {
     PuctArgs a{};
-    sn_status st = puct_args(e, q, a);
+    sn_status st = puct_args(e, q, a, kNeedStats | kNeedHist | kNeedProbs);
     if (st != SN_OK) return st;
     if (r0 < 0 || nr < 1 || !ro_base) return set_error(SN_EINVAL, "need r0 >= 0, nr >= 1 and the dealt states");
     if (!w1s || !w1c || !w2 || !head) return set_error(SN_EINVAL, "NULL argument");
@@ -1841,7 +1861,7 @@ sn_status sn_debug_puct_phases(uint64_t* out, int n) {
 
 sn_status sn_puct_choose(sn_env* e, const sn_puct* q, int32_t* actions, int32_t* best_index, void* stream) {
     PuctArgs a{};
-    sn_status st = puct_args(e, q, a);
+    sn_status st = puct_args(e, q, a, (q && q->n > 1) ? kNeedStats : 0u);  // one-card hands play it directly
     if (st != SN_OK) return st;
     hipLaunchKernelGGL(k_puct_choose, dim3(grid_for(a.D)), dim3(kBlock), 0, (hipStream_t)stream, e->s, a, actions,
                        best_index);

@@ -38,7 +38,7 @@ import torch
 from torch import nn
 
 from . import _native as nat
-from .puct import ROW, BatchedPUCT, ctypes_ref
+from .engine import ROW, BatchedEngine, ctypes_ref
 from .splitk import SplitKLinear, splitk_wgrad, train_forward  # noqa: F401  (re-exported)
 from .utils.nets import MultiHeadedMLP
 
@@ -101,12 +101,12 @@ def distinct_picks(S, rows, k, gen, dev):
     return torch.cat(cols, dim=1)
 
 
-class BatchedACER(BatchedPUCT):
+class BatchedACER(BatchedEngine):
     def __init__(self, env, actor=None, seats_mask=None, net_dtype=torch.bfloat16, seed=0, gamma=0.99, rollout_len=10,
                  minibatch=5, truncate=1.0, warmup=100, r_factor=0.1, critic_weight=1.0, capacity=None,
                  log_epsilon=-20.0, max_decisions=None, max_replay_bytes=None):
         super().__init__(env, actor if actor is not None else make_actor_critic(), seed=seed, seats_mask=seats_mask,
-                         puct_root=False, net_dtype=net_dtype, max_decisions=max_decisions)
+                         net_dtype=net_dtype, max_decisions=max_decisions)
         self.gamma, self.truncate, self.r_factor = float(gamma), float(truncate), float(r_factor)
         self.rollout_len, self.minibatch, self.warmup = int(rollout_len), int(minibatch), int(warmup)
         self.critic_weight, self.log_epsilon = float(critic_weight), float(log_epsilon)
@@ -155,13 +155,9 @@ class BatchedACER(BatchedPUCT):
         self.last_losses = []
 
     # ------------------------------------------------------------ acting
-    def decide(self, n, memorize=False, record=False):
-        """sample every deciding seat's card at hand size n: actions [B, N] int32"""
+    def _decide(self, q, n, record):
+        """sample every deciding seat's card at hand size n"""
         L, h, st = nat.lib(), self.env._h, self.env._stream()
-        if self.D == 0:
-            self.step_id += 1
-            return self.actions
-        q = self._params(n)
         # recording with the actor on this device: the training-precision
         # forward (fp32 rows) is the one sampled from, so the behaviour log pi
         # is that forward's and no second, inference-dtype pass is needed
@@ -199,8 +195,6 @@ class BatchedACER(BatchedPUCT):
                     lt, _ = self.actor(r32.to(self.actor_device()))
                 lt = lt.reshape(self.D, n).to(self.env.device)
             self.rep_logp[s, t, :D, :n] = torch.log_softmax(lt.float(), dim=1)
-        self.step_id += 1
-        return self.actions
 
     def play_episode(self, others=None, record=True):
         """one whole game of every env game (non-deciding seats: uniform moves);
@@ -401,7 +395,7 @@ class BatchedACER(BatchedPUCT):
         self.last_losses += done_updates
         return done_updates
 
-    # ------------------------------------------------------------ the league's protocol (puct.BatchedPUCT)
+    # ------------------------------------------------------------ the league's protocol (engine.BatchedEngine)
     @classmethod
     def from_agent(cls, env, agent, *, seed, net_dtype, slots, seats):
         return cls(env, agent.actor_critic, net_dtype=net_dtype, seed=seed, gamma=agent.gamma,

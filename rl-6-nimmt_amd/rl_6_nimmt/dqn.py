@@ -50,7 +50,7 @@ import torch
 from torch import nn
 
 from . import _native as nat
-from .puct import BatchedPUCT, FusedMLP, ctypes_ref
+from .engine import BatchedEngine, FusedMLP, ctypes_ref
 from .replay import DevicePER
 
 T_STEPS = 10
@@ -180,7 +180,7 @@ def league_capacity(history_length, seats):
 
 
 # ---------------------------------------------------------------- the engine
-class BatchedDQN(BatchedPUCT):
+class BatchedDQN(BatchedEngine):
     def __init__(self, env, q_net, target_net=None, prioritised=False, gamma=0.99, eps_func=None, minibatch=64,
                  updates=T_STEPS, retrain_interval=4, tau=1e-2, capacity=1 << 16, seed=0, net_dtype=torch.bfloat16,
                  seats_mask=None, max_decisions=None, n_steps=1):
@@ -191,8 +191,7 @@ class BatchedDQN(BatchedPUCT):
         from .agents.dqn import eps_func_decay
         from .utils.nets import DuellingDQNNet
 
-        super().__init__(env, q_net, seed=seed, seats_mask=seats_mask, puct_root=False, net_dtype=net_dtype,
-                         max_decisions=max_decisions)
+        super().__init__(env, q_net, seed=seed, seats_mask=seats_mask, net_dtype=net_dtype, max_decisions=max_decisions)
         self.target_net, self.prioritised = target_net, bool(prioritised)
         self.gamma, self.tau = float(gamma), tau
         self.n_steps = int(n_steps)
@@ -267,13 +266,12 @@ class BatchedDQN(BatchedPUCT):
     # ------------------------------------------------------------ acting
     def decide(self, n, memorize=False, record=False):
         """epsilon-greedy card of every deciding seat at hand size n: actions [B, N] int32"""
+        self.eps_used = self.current_eps()  # of a round without a seat too: end_episode logs it
+        return super().decide(n, record=record)
+
+    def _decide(self, q, n, record):
         L, h, st = nat.lib(), self.env._h, self.env._stream()
-        self.eps_used = self.current_eps()
-        if self.D == 0:  # tournament mode: no seat of this agent in the current games
-            self.step_id += 1
-            return self.actions
         D, dev = self.D, self.env.device
-        q = self._params(n)
         self.sync_net()
         obs_t = None
         if record:
@@ -299,8 +297,6 @@ class BatchedDQN(BatchedPUCT):
         if record:
             self._acts[self._t] = self.actions.view(-1)[self.decider_index()]
             self._t += 1
-        self.step_id += 1
-        return self.actions
 
     def rewards_seen(self, per_step, T=None):
         """[T, D] int32: the reward learn() gets at step t is step t-1's (0 at t = 0)"""
@@ -428,7 +424,7 @@ class BatchedDQN(BatchedPUCT):
             losses.append(loss.detach())
         return losses
 
-    # ------------------------------------------------------------ the league's protocol (puct.BatchedPUCT)
+    # ------------------------------------------------------------ the league's protocol (engine.BatchedEngine)
     closes_round = True
 
     @classmethod

@@ -25,8 +25,8 @@ Agents (the pool of run.py:20-40):
     stream (sn_league_step), so a league of DrunkHamster and MCSAgent seats
     replays the reference's seeded Tournament bit for bit (golden F11);
   * PUCTAgent / PolicyMCSAgent, PUCTCustomedAgent, BatchedACERAgent -- one
-    batched engine per agent (puct.BatchedPUCT / BatchedPUCTCustomed,
-    acer.BatchedACER) over the decision list of its seats in the slots'
+    batched engine per agent (an engine.BatchedEngine: puct.BatchedPUCT /
+    BatchedPUCTCustomed, acer.BatchedACER) over the decision list of its seats in the slots'
     current games (sn_puct.dec_list); the policy net runs on PyTorch-ROCm.
     Their random draws are Philox, not torch's CPU generator (parity
     unpinned, like the engines themselves), and they consume no numpy words
@@ -48,7 +48,7 @@ net agent takes one Adam step on its loss summed over the round's games
 (the reference steps once per game: puct.py / acer.py document the batched
 losses).  Nets move to the tournament's device.
 
-The engines are driven through one protocol (puct.BatchedPUCT, overridden
+The engines are driven through one protocol (engine.BatchedEngine, overridden
 where an engine differs; ENGINES maps a net kind to its class): from_agent
 builds the engine of a drop-in agent (hyper-parameters, replay size); a round
 is begin_round(dec, agent, train), ten decide(n, record=train), end_round

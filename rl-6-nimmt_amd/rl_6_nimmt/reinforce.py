@@ -21,36 +21,30 @@ import numpy as np
 import torch
 
 from . import _native as nat
-from .puct import BatchedPUCT, ctypes_ref, decision_forwards, make_actor
+from .engine import BatchedEngine, ctypes_ref, decision_forwards, make_actor
 
 
-class BatchedReinforce(BatchedPUCT):
+class BatchedReinforce(BatchedEngine):
     def __init__(self, env, actor=None, seats_mask=None, net_dtype=torch.bfloat16, seed=0, gamma=0.99, r_factor=1.0,
                  actor_weight=1.0, entropy_weight=0.0, max_decisions=None):
         super().__init__(env, actor if actor is not None else make_actor(), seed=seed, seats_mask=seats_mask,
-                         puct_root=False, net_dtype=net_dtype, max_decisions=max_decisions)
+                         net_dtype=net_dtype, max_decisions=max_decisions)
         self.gamma, self.r_factor = float(gamma), float(r_factor)
         self.actor_weight, self.entropy_weight = float(actor_weight), float(entropy_weight)
         D = self.D_max
         self.log_prob = torch.zeros((D,), dtype=torch.float32, device=env.device)
         self.entropy = torch.zeros((D,), dtype=torch.float32, device=env.device)
 
-    def decide(self, n, memorize=False, record=False):
-        """sample every deciding seat's card at hand size n: actions [B, N] int32"""
-        L, h, st = nat.lib(), self.env._h, self.env._stream()
-        if self.D == 0:  # tournament mode: no seat of this agent in the current games
-            self.step_id += 1
-            return self.actions
-        q = self._params(n)
+    def _decide(self, q, n, record):
+        """sample every deciding seat's card at hand size n"""
         self.sync_net()
         rows = self._root_rows(q, n)
         logits = self._logits(rows)
-        nat.check(L.sn_policy_sample(h, ctypes_ref(q), nat.ptr(logits), nat.ptr(self.actions), nat.ptr(self.best_index),
-                                     nat.ptr(self.log_prob), nat.ptr(self.entropy), st), "sn_policy_sample")
+        nat.check(nat.lib().sn_policy_sample(self.env._h, ctypes_ref(q), nat.ptr(logits), nat.ptr(self.actions),
+                                             nat.ptr(self.best_index), nat.ptr(self.log_prob), nat.ptr(self.entropy),
+                                             self.env._stream()), "sn_policy_sample")
         if record:
-            self.decisions.append((self._train_rows(q, n, rows), n, self.best_index[: self.D].clone()))
-        self.step_id += 1
-        return self.actions
+            self._record(q, n, rows)
 
     def play_episode(self, others=None, record=False):
         """one whole game of every env game (non-deciding seats: uniform

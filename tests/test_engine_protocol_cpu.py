@@ -1,8 +1,9 @@
-"""The engine protocol the batched tournament drives (puct.BatchedPUCT and
+"""The engine protocol the batched tournament drives (engine.BatchedEngine and
 its subclasses; league.py's module docstring), on the host: the decider
 index both modes share, the replay sizing of the league's engines,
-`from_agent`, `inherit`, and that league.py names no engine class in an
-isinstance."""
+`from_agent`, `inherit`, that league.py names no engine class in an
+isinstance, and that only puct.BatchedPUCT carries the search: its buffers,
+its settings and the rollout preparation of `sync_net`."""
 import inspect
 import re
 
@@ -191,3 +192,100 @@ def test_league_names_no_engine_class_in_an_isinstance():
     from rl_6_nimmt import league
 
     assert not re.search(r"isinstance\([^\n]*\bBatched(PUCT|PUCTCustomed|Reinforce|ACER|DQN)\b", inspect.getsource(league))
+
+
+# ---------------------------------------------------------------- the base and the search
+SEARCH_STATE = ("avail", "ro", "stats", "hist", "root_probs", "mc_per_card", "mc_max", "c_puct", "puct_root", "graph",
+                "deal_batch", "fused_rollouts")
+SEARCH_POINTERS = ("avail", "rollouts", "stats", "hist", "root_probs", "step_dev")
+
+
+def _non_search(**kw):
+    """the four engines without a search, built as the league (max_decisions) or a seats mask builds them"""
+    from torch import nn
+
+    from rl_6_nimmt.acer import BatchedACER
+    from rl_6_nimmt.dqn import BatchedDQN
+    from rl_6_nimmt.puct import BatchedPUCTCustomed, make_actor_value
+    from rl_6_nimmt.reinforce import BatchedReinforce
+    from rl_6_nimmt.utils.nets import MultiHeadedMLP
+
+    q_net = MultiHeadedMLP(47, (64,), (104,), nn.ReLU(), (None,))
+    return [BatchedPUCTCustomed(_HostEnv(B, N), make_actor_value(), **kw), BatchedReinforce(_HostEnv(B, N), **kw),
+            BatchedACER(_HostEnv(B, N), **kw), BatchedDQN(_HostEnv(B, N), q_net, capacity=64, **kw)]
+
+
+def _puct(**kw):
+    from rl_6_nimmt.puct import BatchedPUCT, make_actor
+
+    return BatchedPUCT(_HostEnv(B, N), make_actor(), **kw)
+
+
+def test_only_the_search_engine_is_a_batched_puct():
+    from rl_6_nimmt.engine import BatchedEngine
+    from rl_6_nimmt.puct import BatchedPUCT
+
+    assert issubclass(BatchedPUCT, BatchedEngine)
+    for eng in _non_search(max_decisions=12):
+        assert isinstance(eng, BatchedEngine) and not isinstance(eng, BatchedPUCT), type(eng).__name__
+
+
+@pytest.mark.parametrize("kw", [{"max_decisions": 12}, {"seats_mask": MASK}], ids=["listed", "masked"])
+def test_non_search_engines_carry_no_search_state(kw):
+    for eng in _non_search(**kw):
+        name = type(eng).__name__
+        assert [a for a in SEARCH_STATE if hasattr(eng, a)] == [], name
+        eng.seed, eng.step_id = 7, 3
+        q = eng._params(4)
+        assert [f for f in SEARCH_POINTERS if getattr(q, f) is not None] == [], name
+        assert (q.seats_mask, q.n, q.seed, q.step) == (eng.seats_mask, 4, 7, 3), name
+        if "max_decisions" in kw:
+            assert q.dec_list is None and q.num_dec == 0 and eng.D == 0, name
+            eng.use_decisions(DEC)
+            q = eng._params(4)
+            assert q.num_dec == 3 and q.dec_list == eng.dec.data_ptr() and eng.D == 3, name
+        else:
+            assert q.dec_list is None and q.num_dec == 0 and eng.D == B * len(SEATS), name
+
+
+def test_batched_puct_keeps_its_search_state():
+    eng = _puct(max_decisions=12)
+    shapes = {"ro": (12, 48), "stats": (12, 24), "hist": (12, 172), "root_probs": (12, 10), "avail": (4, B * N)}
+    assert {a: tuple(getattr(eng, a).shape) for a in shapes} == shapes
+    assert all(hasattr(eng, a) for a in SEARCH_STATE)
+    q = eng._params(4)
+    for field, attr in (("avail", "avail"), ("rollouts", "ro"), ("stats", "stats"), ("hist", "hist"),
+                        ("root_probs", "root_probs")):
+        assert getattr(q, field) == getattr(eng, attr).data_ptr(), field
+    assert q.step_dev is None and q.puct_root == 1 and q.c_puct == 2.0
+    assert eng._params(4, step_dev=True).step_dev == eng._step_dev.data_ptr()
+    assert eng._params(4, rollout=5).rollout == 5
+
+
+def test_decide_without_a_seat_makes_no_native_call(monkeypatch):
+    from rl_6_nimmt import _native
+
+    def no_lib():
+        raise AssertionError("a native call without a deciding seat")
+
+    monkeypatch.setattr(_native, "lib", no_lib)
+    for eng in _non_search(max_decisions=12) + [_puct(max_decisions=12)]:
+        assert eng.D == 0
+        before = eng.step_id
+        assert eng.decide(4, memorize=False, record=True) is eng.actions, type(eng).__name__
+        assert eng.step_id == before + 1, type(eng).__name__
+
+
+def test_only_the_search_prepares_rollouts_in_sync_net():
+    """the default actor in bf16 has the one-kernel rollout form (FusedMLP.fused): BatchedPUCT packs it and
+    allocates the rollout logits when it builds its copy of the net, an engine that never rolls out does neither"""
+    from rl_6_nimmt.reinforce import BatchedReinforce
+
+    rf = BatchedReinforce(_HostEnv(B, N), max_decisions=12, net_dtype=torch.bfloat16)
+    net = rf.sync_net()
+    assert net is rf._net and not hasattr(rf, "_fbufs") and not hasattr(net, "_fused")
+    assert net.fused() is not None  # the pack exists for this net: nobody asked for it until now
+    eng = _puct(max_decisions=12, net_dtype=torch.bfloat16)
+    net = eng.sync_net()
+    assert getattr(net, "_fused", None) is not None
+    assert eng._fbufs.numel() == eng.D_max * N * 10 == 12 * 4 * 10

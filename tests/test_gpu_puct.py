@@ -886,3 +886,107 @@ def test_puct_search_at_configured_budget_matches_reference_in_law():
         check(f"chosen_rank@{n}", best,
               np.array([r["dec"][str(n)]["legal"].index(r["dec"][str(n)]["chosen"]) for r in games], dtype=np.float64))
     print("F14b (ours, reference, paired s.e.):", report)
+
+
+# ---------------------------------------------------------------- which calls need sn_puct's search buffers
+SEARCH_FIELDS = ("avail", "rollouts", "stats", "hist", "root_probs")
+SENTINEL = 0x5A5A5A5A
+
+
+def _reinforce_handle(mode):
+    """a BatchedReinforce (its sn_puct carries no search buffer) on a fresh deal: every game's seats 0 and 2
+    (D = 10), or the decision list [9, 1, 6] of a 3-game handle"""
+    from rl_6_nimmt.reinforce import BatchedReinforce
+    from rl_6_nimmt.vec_env import VecSechsNimmtEnv
+
+    env = VecSechsNimmtEnv(5 if mode == "masked" else 3, 4, seed=3, rng="philox")
+    env.reset()
+    if mode == "masked":
+        eng = BatchedReinforce(env, seats_mask=0b0101, seed=11)
+    else:
+        eng = BatchedReinforce(env, max_decisions=12, seed=11)
+        eng.use_decisions([9, 1, 6])
+    assert eng.D == (10 if mode == "masked" else 3)
+    assert all(getattr(eng._params(10), f) is None for f in SEARCH_FIELDS)
+    return env, eng
+
+
+@pytest.mark.parametrize("mode", ["masked", "listed"])
+def test_non_search_kernels_leave_the_search_buffers_alone(mode):
+    """include/sechs.h at sn_puct: the search buffers may be NULL for sn_puct_root_rows, sn_policy_sample,
+    sn_pcv_choose, sn_dqn_obs and sn_dqn_select.  Every output of those calls is bit-equal between a struct
+    with NULL buffers and one pointing at sentinel-filled buffers, and no sentinel word changes."""
+    import ctypes
+
+    from rl_6_nimmt import _native as nat
+
+    env, eng = _reinforce_handle(mode)
+    dev, n, D, BN = env.device, 10, eng.D, env.num_games * env.num_players
+    words = {"avail": 4 * BN, "rollouts": D * 48, "stats": D * 24, "hist": D * 172, "root_probs": D * 10}
+    sentinels = {f: torch.full((w,), SENTINEL, dtype=torch.int32, device=dev) for f, w in words.items()}
+    q_null, q_sent = eng._params(n), eng._params(n)
+    for f, buf in sentinels.items():
+        setattr(q_sent, f, buf.data_ptr())
+    logits = torch.linspace(-2.0, 2.0, D * n, device=dev)
+    heads = torch.linspace(-1.0, 3.0, D * n * 2, device=dev).reshape(D * n, 2).contiguous()
+    qvals = (torch.linspace(-5.0, 5.0, D * 104, device=dev) % 1.7).reshape(D, 104).contiguous()
+    L, h, st = nat.lib(), env._h, env._stream()
+
+    def run(q):
+        r = ctypes.byref(q)
+        i32 = lambda *shape: torch.full(shape, -7, dtype=torch.int32, device=dev)  # noqa: E731
+        f32 = lambda *shape: torch.full(shape, -7.0, dtype=torch.float32, device=dev)  # noqa: E731
+        out = {"rows": f32(D * n, 48), "rows_bf16": torch.zeros((D * n, 48), dtype=torch.bfloat16, device=dev),
+               "obs": torch.zeros((D, 48), dtype=torch.int8, device=dev), "states": f32(D, 48)}
+        nat.check(L.sn_puct_root_rows(h, r, nat.ptr(out["rows"]), 0, st), "sn_puct_root_rows")
+        nat.check(L.sn_puct_root_rows(h, r, nat.ptr(out["rows_bf16"]), 1, st), "sn_puct_root_rows")
+        for name in ("sample", "pcv", "dqn"):
+            out.update({f"{name}_actions": i32(env.num_games, env.num_players), f"{name}_index": i32(D),
+                        f"{name}_a": f32(D), f"{name}_b": f32(D)})
+        nat.check(L.sn_policy_sample(h, r, nat.ptr(logits), nat.ptr(out["sample_actions"]), nat.ptr(out["sample_index"]),
+                                     nat.ptr(out["sample_a"]), nat.ptr(out["sample_b"]), st), "sn_policy_sample")
+        nat.check(L.sn_pcv_choose(h, r, nat.ptr(heads), nat.ptr(out["pcv_actions"]), nat.ptr(out["pcv_index"]),
+                                  nat.ptr(out["pcv_a"]), nat.ptr(out["pcv_b"]), st), "sn_pcv_choose")
+        nat.check(L.sn_dqn_obs(h, r, nat.ptr(out["obs"]), nat.ptr(out["states"]), 0, st), "sn_dqn_obs")
+        nat.check(L.sn_dqn_select(h, r, nat.ptr(qvals), 104, 0.3, nat.ptr(out["dqn_actions"]), nat.ptr(out["dqn_index"]),
+                                  nat.ptr(out["dqn_a"]), st), "sn_dqn_select")
+        torch.cuda.synchronize()
+        return {k: v.cpu() for k, v in out.items()}
+
+    got_null, got_sent = run(q_null), run(q_sent)
+    for k, v in got_null.items():
+        assert torch.equal(v.view(torch.uint8), got_sent[k].view(torch.uint8)), k  # bit for bit
+    flat = eng.decider_index().cpu()
+    for name in ("sample", "pcv", "dqn"):  # the calls ran: every deciding seat got a card, every decision an index
+        assert bool((got_null[f"{name}_actions"].view(-1)[flat] >= 0).all()), name
+        assert bool((got_null[f"{name}_index"] >= 0).all()), name
+    for f, buf in sentinels.items():
+        assert bool((buf == SENTINEL).all()), f
+
+
+@pytest.mark.parametrize("mode", ["masked", "listed"])
+def test_search_calls_refuse_a_struct_without_their_buffers(mode):
+    """the calls that read or write a search buffer check it on the host: SN_EINVAL naming the first missing
+    field, and nothing is launched (no kernel ever sees a NULL buffer here)"""
+    import ctypes
+
+    from rl_6_nimmt import _native as nat
+
+    env, eng = _reinforce_handle(mode)
+    L, h, st = nat.lib(), env._h, env._stream()
+    q, q2 = eng._params(10), eng._params(2)
+    logits = torch.zeros((eng.D * env.num_players * 10,), dtype=torch.float32, device=env.device)
+    lp, r, r2 = nat.ptr(logits), ctypes.byref(q), ctypes.byref(q2)
+    calls = [("sn_puct_init", "stats", lambda: L.sn_puct_init(h, r, lp, st)),
+             ("sn_puct_deal", "avail", lambda: L.sn_puct_deal(h, r, st)),
+             ("sn_puct_deal_batch", "avail", lambda: L.sn_puct_deal_batch(h, r, 0, 1, lp, st)),
+             ("sn_puct_rows", "rollouts", lambda: L.sn_puct_rows(h, r, 10, lp, 0, st)),
+             ("sn_puct_step", "rollouts", lambda: L.sn_puct_step(h, r, lp, 0, 10, st)),
+             ("sn_puct_mlp_seats", "rollouts", lambda: L.sn_puct_mlp_seats(h, r, 10, lp, lp, lp, lp, lp, st)),
+             ("sn_puct_rollouts", "stats", lambda: L.sn_puct_rollouts(h, r, 0, 1, lp, lp, lp, lp, lp, st)),
+             ("sn_puct_choose", "stats", lambda: L.sn_puct_choose(h, r2, nat.ptr(eng.actions), None, st))]
+    for name, field, call in calls:
+        assert call() == nat.SN_EINVAL, name
+        assert f"sn_puct.{field} is NULL" in L.sn_last_error().decode(), (name, L.sn_last_error())
+    torch.cuda.synchronize()
+    assert bool((eng.actions == 0).all()) and bool((logits == 0).all())
