@@ -486,7 +486,12 @@ sn_status sn_puct_deal_batch(sn_env* env, const sn_puct* q, int r0, int nr, void
    minimum) runs every step (sn_puct_mlp_seats' rows, MFMA layer 1 + 2 and
    head into logits in LDS, then sn_puct_step's seat-lane step) of each
    rollout in order -- the same values as the launch-per-step loop (3 <= N
-   <= 8; weights as sn_puct_mlp_seats). */
+   <= 8; weights as sn_puct_mlp_seats).  The environment variable
+   SECHS_PUCT_GROUP=k forces k decisions per group (clamped to 1 .. 32 / L),
+   read at every call: the same values at any group size (A/B runs, tests).
+   Its siblings: SECHS_PUCT_STEP_SEATS=0 (sn_puct_step runs the one-lane-per-
+   decision kernel at N <= 8 too), and in the Python engine
+   SECHS_PUCT_DEAL_BATCH / SECHS_PUCT_ROLLOUTS (puct.py). */
 sn_status sn_puct_rollouts(sn_env* env, const sn_puct* q, int r0, int nr, void* ro_base, const void* w1s,
                            const float* w1c, const void* w2, const float* head, void* stream);
 sn_status sn_puct_rows(sn_env* env, const sn_puct* q, int n_cur, void* rows, int bf16, void* stream);

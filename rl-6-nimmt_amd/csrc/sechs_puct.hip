@@ -1825,7 +1825,10 @@ sn_status sn_puct_rollouts(sn_env* e, const sn_puct* q, int r0, int nr, void* ro
     const int dg_max = kRollSeats / Lw;
     const int64_t slots = 8ll * e->cus;  // one 8-wave workgroup per CU
     const int64_t rounds = std::max<int64_t>(1, (a.D + dg_max * slots - 1) / (dg_max * slots));
-    const int dg = (int)std::min<int64_t>(dg_max, std::max<int64_t>(1, (a.D + rounds * slots - 1) / (rounds * slots)));
+    int dg = (int)std::min<int64_t>(dg_max, std::max<int64_t>(1, (a.D + rounds * slots - 1) / (rounds * slots)));
+    // SECHS_PUCT_GROUP=k: k decisions per group (clamped to 1 .. kRollSeats / L) whatever the device's
+    // size -- the multi-decision groups at a small D (A/B, tests); unset: the sizing above
+    if (const char* gv = getenv("SECHS_PUCT_GROUP"); gv && gv[0]) dg = std::min(dg_max, std::max(1, atoi(gv)));
     const int64_t groups = (a.D + dg - 1) / dg;
     const dim3 grid((unsigned)std::min<int64_t>((groups + 7) / 8, (int64_t)e->cus));
 #define SN_ROLLOUTS(NN_, L_)                                                                                  \

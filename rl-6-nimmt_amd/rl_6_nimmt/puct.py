@@ -58,7 +58,8 @@ class BatchedPUCT(BatchedEngine):
         # whole rollouts in one kernel per deal batch (sn_puct_rollouts: a wave per group of 8
         # decisions, logits in LDS; round 6: 1.10 G playout env-steps/s on config 4, and the
         # tournament's engines too) or a launch per step (fused_rollouts=False);
-        # SECHS_PUCT_ROLLOUTS=0 / 1 overrides (A/B runs, tests)
+        # SECHS_PUCT_ROLLOUTS=0 / 1 overrides (A/B runs, tests); SECHS_PUCT_GROUP=k (read by
+        # sn_puct_rollouts itself) forces k decisions per wave's group instead of the device-sized count
         env_ro = os.environ.get("SECHS_PUCT_ROLLOUTS")
         self.fused_rollouts = (env_ro != "0") if env_ro is not None else (True if fused_rollouts is None
                                                                             else bool(fused_rollouts))

@@ -680,8 +680,11 @@ def test_fused_rollouts_equal_step_launches(monkeypatch):
     logits in LDS) and the launch-per-step loop (sn_puct_mlp_seats +
     sn_puct_step) compute the same logits and draw the same uniforms: a
     whole PUCT search gives identical statistics, histograms and moves --
-    4 players (one 16-decision group per 64 seats) and 3 players (48 live
-    seat rows per group), a ragged last group"""
+    4 players and 3 players (three of every four seat lanes live).  A wave
+    carries a group of up to 32 / L decisions (8 here) whose size the
+    library fits to the device: on a part of 256 compute units these
+    decision counts run one decision per group; the larger groups are
+    pinned in tests/test_gpu_puct_players.py"""
     for N, B in [(4, 300), (3, 97)]:
         res = {}
         for rollouts in ("1", "0"):
@@ -717,26 +720,19 @@ def _bf16_forward_bound(x, layers, head_w, head_b, u=2.0 ** -8, l1_roundings=2):
     return logit, e
 
 
-@pytest.mark.parametrize("n", [10, 6, 3])
-def test_mlp_seats_kernel_matches_fp32_reference_net(n):
-    """VERDICT r04 #2a: sn_puct_mlp_seats -- the MFMA kernel behind every
-    rollout logit of config 4 -- on the reference-recorded F8 weights
-    (torch.manual_seed(0); PUCTAgent(), utils/nets.py:100-132), at every
-    n_cur of rollouts from positions with n cards left, against the f64
-    reference forward of the SAME normalised rows (sn_puct_rows in f32 --
-    exact vs SechsNimmtStateNormalization, test_root_rows_are_normalised_
-    observations): every logit within the derived first-order bf16 bound
-    (x 1.25 for the second-order terms), and every candidate's softmax
-    probability (mcts.py:219-228) within p * (exp(2 * 1.25 * max bound) - 1).
-    (Layer 1 is factored per seat: two bf16 roundings.)"""
+def _check_mlp_seats_against_f64_net(B, N, n):
+    """sn_puct_mlp_seats on the F8 weights at every n_cur of rollouts from positions with n cards left (every
+    seat of B games of N players deciding) against the f64 forward of the same f32 rows: every logit within
+    1.25 x _bf16_forward_bound, every softmax probability within the bound that follows; returns the worst
+    probability error"""
     import ctypes
 
     from rl_6_nimmt import _native as nat
 
     z = np.load(os.path.join(GOLDEN, "puct_policy.npz"))
     weights = {k: torch.from_numpy(z[k]) for k in z.files if "net" in k}
-    env, eng = _engine(B=512, dtype=torch.bfloat16, mc_max=4, mc_per_card=2, seed=31, weights=weights)
-    N = env.num_players
+    env, eng = _engine(B=B, N=N, dtype=torch.bfloat16, mc_max=4, mc_per_card=2, seed=31, weights=weights)
+    assert N == env.num_players
     for t in range(10 - n):
         env.step(eng.decide(10 - t))
     net = eng.sync_net()
@@ -767,7 +763,34 @@ def test_mlp_seats_kernel_matches_fp32_reference_net(n):
             lim = pr * (torch.exp(2 * 1.25 * bound.view(-1, m).max(dim=1, keepdim=True).values) - 1) + 1e-7
             assert ((p - pr).abs() <= lim).all(), (kern, m)
             worst_dp = max(worst_dp, float((p - pr).abs().max()))
+    return worst_dp
+
+
+@pytest.mark.parametrize("n", [10, 6, 3])
+def test_mlp_seats_kernel_matches_fp32_reference_net(n):
+    """VERDICT r04 #2a: sn_puct_mlp_seats -- the MFMA kernel behind every
+    rollout logit of config 4 -- on the reference-recorded F8 weights
+    (torch.manual_seed(0); PUCTAgent(), utils/nets.py:100-132), at every
+    n_cur of rollouts from positions with n cards left, against the f64
+    reference forward of the SAME normalised rows (sn_puct_rows in f32 --
+    exact vs SechsNimmtStateNormalization, test_root_rows_are_normalised_
+    observations): every logit within the derived first-order bf16 bound
+    (x 1.25 for the second-order terms), and every candidate's softmax
+    probability (mcts.py:219-228) within p * (exp(2 * 1.25 * max bound) - 1).
+    (Layer 1 is factored per seat: two bf16 roundings.)"""
+    worst_dp = _check_mlp_seats_against_f64_net(512, 4, n)
     assert worst_dp < 0.02, worst_dp  # the derived bound is loose; the kernel is far inside it
+
+
+@pytest.mark.parametrize("N,B,n", [(N, 131, n) for N in (2, 3, 5, 7, 10) for n in (10, 3)] + [(7, 677, 3)])
+def test_mlp_seats_kernel_matches_fp32_reference_net_at_other_player_counts(N, B, n):
+    """the same check (same F8 weights, same f64 forward, same derived bound) where the player count does not
+    divide the kernel's 64-seat groups, so a decision's seats straddle two groups (seat i belongs to decision
+    i / N): every seat of B games deciding -- B N^2 seats, neither a multiple of 64 nor of 64 N.  B = 677 at
+    N = 7 is 519 groups: more than two workgroups per compute unit of a 256-CU part take, so some loop on to
+    a second group (the loads issued one group ahead)."""
+    assert (B * N * N) % 64 and (B * N * N) % (64 * N)
+    _check_mlp_seats_against_f64_net(B, N, n)
 
 
 def test_puct_search_statistics_match_reference_in_law():
