@@ -689,6 +689,40 @@ sn_status sn_dqn_unpack_nstep(int64_t n, const void* rows, float* states, float*
 sn_status sn_dqn_target(int64_t n, const float* q_next_local, const float* q_next_target, int64_t stride,
                         const float* reward, const float* not_done, double gamma, float* target, void* stream);
 
+/* The noisy DQN nets (NoisyFactorizedLinear, utils/nets.py:36-63): factorised
+   Gaussian noise of its own for every decision row.  For decision d (game g,
+   seat p of the handle, q's deciders in sn_dqn_select's order), linear layer l
+   (forward order: the latent layers, then the heads; l < 64) and side s
+   (0: the layer's inputs, 1: its outputs):
+     tag = SN_NOISY_TAG(l, s) = 0xFFF00 + 2 l + s,
+     Philox4x32-10 key (seed_lo ^ step, seed_hi), counter (i, 0, stream lo,
+     stream hi) with stream = gid << 32 | p << 28 | tag << 8 and gid =
+     game_offset + g; the block's words o give the units 2 i and 2 i + 1:
+       u1 = ((o[0] >> 8) + 1) * 2^-24 in (0, 1],  u2 = (o[1] >> 8) * 2^-24,
+       r = sqrtf(-2 logf(u1)),  n = r cosf(2 pi u2), r sinf(2 pi u2)
+     in fp32 with the accurate library functions (|n| <= sqrt(48 ln 2)), and
+     the value used is e = sign(n) sqrt|n|.
+   The noise depends on (seed, step, global game, seat, layer, side, unit)
+   only.  Every call returns SN_EINVAL for a NULL handle or pointer, width < 1
+   or a tag outside SN_NOISY_TAG(0, 0) .. SN_NOISY_TAG(63, 1).  One lane per
+   (row, unit pair).
+   sn_noisy_eps: out [D][width] f32 = e of the units 0 .. width - 1. */
+#define SN_NOISY_TAG(layer, side) (0xFFF00 + 2 * (layer) + (side))
+sn_status sn_noisy_eps(sn_env* env, const sn_puct* q, int64_t tag, int64_t width, float* out, void* stream);
+/* out[d][k] = x[d][k] * e_k for k < width: the product in fp32, rounded once to
+   the dtype of x and out (bf16 != 0: bfloat16, else f32).  Rows of x_stride /
+   out_stride elements, both >= width (else SN_EINVAL); x and out lie apart. */
+sn_status sn_noisy_scale(sn_env* env, const sn_puct* q, int64_t tag, const void* x, int64_t x_stride, int64_t width,
+                         int bf16, void* out, int64_t out_stride, void* stream);
+/* Over the columns j = col0 .. col0 + width - 1 of rows of `stride` floats
+   (inside the row, else SN_EINVAL): out[d][j] = mu[d][j] + e_{j - col0} *
+   (sg[d][j] + sigma_b[j]) in fp32 in that order, every operation rounded (no
+   fma): bit-equal to the torch fp32 expression; then max(., 0) if relu.
+   sigma_b is indexed by the column j itself.  out may be mu; the other columns
+   are left as they are. */
+sn_status sn_noisy_combine(sn_env* env, const sn_puct* q, int64_t tag, const float* mu, const float* sg, int64_t stride,
+                           int64_t col0, int64_t width, const float* sigma_b, int relu, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

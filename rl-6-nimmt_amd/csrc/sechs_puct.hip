@@ -1481,6 +1481,116 @@ __global__ void k_dqn_select_duel(DevState s, PuctArgs a, const float* heads, in
     if (value) value[d] = v;
 }
 
+// ---- the noisy DQN nets (utils/nets.py NoisyFactorizedLinear; rl_6_nimmt/dqn.py) ----
+// Every decision row has its own factorised noise: per linear layer l (forward
+// order) one vector over the layer's inputs (side 0) and one over its outputs
+// (side 1).  Philox keyed as k_dqn_select's (seed ^ step, game, seat) with the
+// rollout tag 0xFFF00 + 2 l + side, l < 64: below 0xFFFFE / 0xFFFFF and above
+// any PUCT rollout's.  Counter word 0 is the pair index i: block i gives the
+// units 2 i and 2 i + 1 by Box-Muller in fp32 with the accurate logf / cosf /
+// sinf; u1 in (0, 1], so |normal| <= sqrt(48 ln 2).  The value used is
+// e = sign(normal) * sqrt|normal|.
+constexpr uint32_t kNoisyTag0 = 0xFFF00u;
+constexpr uint32_t kNoisyLayers = 64u;
+
+__device__ __forceinline__ float in_f32(float v) { return v; }
+__device__ __forceinline__ float in_f32(__hip_bfloat16 v) { return __bfloat162float(v); }
+__device__ __forceinline__ float noisy_shape(float n) { return copysignf(sqrtf(fabsf(n)), n); }
+
+__device__ __forceinline__ float2 noisy_pair(const DevState& s, const PuctArgs& a, int64_t d, uint32_t tag, uint32_t i) {
+    int64_t g;
+    int p;
+    dec_to_gp(a, d, g, p);
+    const uint64_t gid = s.game_offset + (uint64_t)g;
+    const uint64_t stream = ((uint64_t)(uint32_t)gid << 32) | ((uint64_t)p << 28) | ((uint64_t)tag << 8);
+    const u32x4 o = philox4x32_10(i, 0u, (uint32_t)stream, (uint32_t)(stream >> 32), a.seed_lo ^ puct_step_of(a),
+                                  a.seed_hi);
+    const float u1 = (float)((o.x >> 8) + 1u) * (1.0f / 16777216.0f), u2 = (float)(o.y >> 8) * (1.0f / 16777216.0f);
+    const float r = sqrtf(-2.0f * logf(u1));
+    const float t = 6.283185307179586f * u2;
+    return float2{noisy_shape(r * cosf(t)), noisy_shape(r * sinf(t))};
+}
+
+// One lane per (decision row, unit pair), adjacent lanes on adjacent pairs of
+// a row; an odd width uses half of its last pair.
+#define SN_NOISY_LANE(width)                                                   \
+    const int P = ((width) + 1) >> 1;                                          \
+    const int64_t lane_id = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;    \
+    if (lane_id >= a.D * P) return;                                            \
+    const int64_t d = lane_id / P;                                             \
+    const int i = (int)(lane_id - d * P);                                      \
+    const bool both = 2 * i + 1 < (width)
+
+__global__ void k_noisy_eps(DevState s, PuctArgs a, uint32_t tag, int width, float* __restrict__ out) {
+    SN_NOISY_LANE(width);
+    const float2 e = noisy_pair(s, a, d, tag, (uint32_t)i);
+    float* o = out + d * width + 2 * i;
+    o[0] = e.x;
+    if (both) o[1] = e.y;
+}
+
+// out[d][k] = x[d][k] * e_k, the product in fp32 rounded once to T.  VEC: both
+// rows start pair-aligned (base pointers and strides), a pair is one access.
+template <typename T, bool VEC>
+__global__ void k_noisy_scale(DevState s, PuctArgs a, uint32_t tag, const T* __restrict__ x, int64_t x_stride,
+                              int width, T* __restrict__ out, int64_t out_stride) {
+    SN_NOISY_LANE(width);
+    const float2 e = noisy_pair(s, a, d, tag, (uint32_t)i);
+    const T* src = x + d * x_stride + 2 * i;
+    T* dst = out + d * out_stride + 2 * i;
+    if (VEC && both) {
+        if constexpr (std::is_same<T, float>::value) {
+            const float2 v = *reinterpret_cast<const float2*>(src);
+            *reinterpret_cast<float2*>(dst) = float2{v.x * e.x, v.y * e.y};
+        } else {
+            const uint32_t v = *reinterpret_cast<const uint32_t*>(src);
+            const float lo = __uint_as_float(v << 16) * e.x, hi = __uint_as_float(v & 0xFFFF0000u) * e.y;
+            *reinterpret_cast<uint32_t*>(dst) = (uint32_t)__bfloat16_as_ushort(__float2bfloat16(lo)) |
+                                                ((uint32_t)__bfloat16_as_ushort(__float2bfloat16(hi)) << 16);
+        }
+        return;
+    }
+    dst[0] = to_out<T>(in_f32(src[0]) * e.x);
+    if (both) dst[1] = to_out<T>(in_f32(src[1]) * e.y);
+}
+
+// out[d][j] = mu[d][j] + e_{j - col0} * (sg[d][j] + sigma_b[j]) over the columns
+// col0 .. col0 + width - 1, fp32 in that order, every operation rounded (no
+// fma), then max(., 0) if relu.  out may be mu.  VEC: col0, the stride and the
+// pointers are pair-aligned.
+template <bool VEC>
+__global__ void k_noisy_combine(DevState s, PuctArgs a, uint32_t tag, const float* mu, const float* sg, int64_t stride,
+                                int col0, int width, const float* __restrict__ sigma_b, int relu, float* out) {
+#pragma clang fp contract(off)
+    SN_NOISY_LANE(width);
+    const float2 e = noisy_pair(s, a, d, tag, (uint32_t)i);
+    const int j = col0 + 2 * i;
+    const int64_t at = d * stride + j;
+    if (VEC && both) {
+        const float2 m = *reinterpret_cast<const float2*>(mu + at), g = *reinterpret_cast<const float2*>(sg + at);
+        const float2 b = *reinterpret_cast<const float2*>(sigma_b + j);
+        const float s0 = g.x + b.x, s1 = g.y + b.y;
+        const float n0 = e.x * s0, n1 = e.y * s1;
+        float v0 = m.x + n0, v1 = m.y + n1;
+        if (relu) v0 = fmaxf(v0, 0.f), v1 = fmaxf(v1, 0.f);
+        *reinterpret_cast<float2*>(out + at) = float2{v0, v1};
+        return;
+    }
+    {
+        const float s0 = sg[at] + sigma_b[j];
+        const float n0 = e.x * s0;
+        const float v0 = mu[at] + n0;
+        out[at] = relu ? fmaxf(v0, 0.f) : v0;
+    }
+    if (both) {
+        const float s1 = sg[at + 1] + sigma_b[j + 1];
+        const float n1 = e.y * s1;
+        const float v1 = mu[at + 1] + n1;
+        out[at + 1] = relu ? fmaxf(v1, 0.f) : v1;
+    }
+}
+#undef SN_NOISY_LANE
+
 // Replay rows of one episode: row (t, d) = [obs[t][d] | obs[t+1][d] | action,
 // done, hand size, 0 | reward i32 | 0, 0].  One lane per 16-byte piece,
 // consecutive lanes on consecutive pieces of a row (as k_per_store).
@@ -2010,6 +2120,72 @@ sn_status sn_dqn_target(int64_t n, const float* q_next_local, const float* q_nex
     hipLaunchKernelGGL(k_dqn_target, dim3((unsigned)((n + kBlock / 64 - 1) / (kBlock / 64))), dim3(kBlock), 0,
                        (hipStream_t)stream, n, q_next_local, q_next_target, stride, reward, not_done, (float)gamma,
                        target);
+    HIP_TRY(hipGetLastError());
+    return SN_OK;
+}
+
+// the noise kernels' shared argument checks: the decider arguments, a tag of layer < 64, a width
+static sn_status noisy_args(sn_env* e, const sn_puct* q, PuctArgs& a, int64_t tag, int64_t width) {
+    sn_status st = puct_args(e, q, a);
+    if (st != SN_OK) return st;
+    if (tag < kNoisyTag0 || tag >= kNoisyTag0 + 2 * kNoisyLayers)
+        return set_error(SN_EINVAL, "tag must be 0xFFF00 + 2 * layer + side with layer < 64");
+    if (width < 1 || width > 0x3FFFFFFF) return set_error(SN_EINVAL, "width must be >= 1");
+    return SN_OK;
+}
+static unsigned noisy_grid(const PuctArgs& a, int64_t width) { return grid_for(a.D * ((width + 1) / 2)); }
+
+sn_status sn_noisy_eps(sn_env* e, const sn_puct* q, int64_t tag, int64_t width, float* out, void* stream) {
+    if (!out) return set_error(SN_EINVAL, "NULL argument");
+    PuctArgs a{};
+    sn_status st = noisy_args(e, q, a, tag, width);
+    if (st != SN_OK) return st;
+    hipLaunchKernelGGL(k_noisy_eps, dim3(noisy_grid(a, width)), dim3(kBlock), 0, (hipStream_t)stream, e->s, a,
+                       (uint32_t)tag, (int)width, out);
+    HIP_TRY(hipGetLastError());
+    return SN_OK;
+}
+
+sn_status sn_noisy_scale(sn_env* e, const sn_puct* q, int64_t tag, const void* x, int64_t x_stride, int64_t width,
+                         int bf16, void* out, int64_t out_stride, void* stream) {
+    if (!x || !out) return set_error(SN_EINVAL, "NULL argument");
+    PuctArgs a{};
+    sn_status st = noisy_args(e, q, a, tag, width);
+    if (st != SN_OK) return st;
+    if (x_stride < width || out_stride < width) return set_error(SN_EINVAL, "a row stride is shorter than the width");
+    const uintptr_t pair = bf16 ? 3 : 7;  // a pair's bytes - 1
+    const bool vec = (((uintptr_t)x | (uintptr_t)out) & pair) == 0 && ((x_stride | out_stride) & 1) == 0;
+    const dim3 grid(noisy_grid(a, width)), block(kBlock);
+    hipStream_t hs = (hipStream_t)stream;
+#define SN_SCALE(T, V)                                                                                              \
+    hipLaunchKernelGGL((k_noisy_scale<T, V>), grid, block, 0, hs, e->s, a, (uint32_t)tag, (const T*)x, x_stride, \
+                       (int)width, (T*)out, out_stride)
+    if (bf16) {
+        if (vec) SN_SCALE(__hip_bfloat16, true); else SN_SCALE(__hip_bfloat16, false);
+    } else {
+        if (vec) SN_SCALE(float, true); else SN_SCALE(float, false);
+    }
+#undef SN_SCALE
+    HIP_TRY(hipGetLastError());
+    return SN_OK;
+}
+
+sn_status sn_noisy_combine(sn_env* e, const sn_puct* q, int64_t tag, const float* mu, const float* sg, int64_t stride,
+                           int64_t col0, int64_t width, const float* sigma_b, int relu, float* out, void* stream) {
+    if (!mu || !sg || !sigma_b || !out) return set_error(SN_EINVAL, "NULL argument");
+    PuctArgs a{};
+    sn_status st = noisy_args(e, q, a, tag, width);
+    if (st != SN_OK) return st;
+    if (col0 < 0 || stride > 0x7FFFFFFF || col0 > stride - width)
+        return set_error(SN_EINVAL, "the columns col0 .. col0 + width - 1 must lie inside a row of `stride` floats");
+    const bool vec = (((uintptr_t)mu | (uintptr_t)sg | (uintptr_t)sigma_b | (uintptr_t)out) & 7) == 0 &&
+                     ((stride | col0) & 1) == 0;
+    if (vec)
+        hipLaunchKernelGGL(k_noisy_combine<true>, dim3(noisy_grid(a, width)), dim3(kBlock), 0, (hipStream_t)stream, e->s,
+                           a, (uint32_t)tag, mu, sg, stride, (int)col0, (int)width, sigma_b, relu, out);
+    else
+        hipLaunchKernelGGL(k_noisy_combine<false>, dim3(noisy_grid(a, width)), dim3(kBlock), 0, (hipStream_t)stream, e->s,
+                           a, (uint32_t)tag, mu, sg, stride, (int)col0, (int)width, sigma_b, relu, out);
     HIP_TRY(hipGetLastError());
     return SN_OK;
 }

@@ -135,6 +135,9 @@ SIGNATURES = {
     "sn_dqn_select_duel": ([_P, _P, _P, _I64, _I64, _I64, ctypes.c_double, _P, _P, _P, _P], _I),
     "sn_dqn_pack_nstep": ([_I64, _I64, _I64, SnDqnGpow, _P, _P, _P, _P, _P], _I),
     "sn_dqn_unpack_nstep": ([_I64, _P, _P, _P, _P, _P, _P, _P], _I),
+    "sn_noisy_eps": ([_P, _P, _I64, _I64, _P, _P], _I),
+    "sn_noisy_scale": ([_P, _P, _I64, _P, _I64, _I64, _I, _P, _I64, _P], _I),
+    "sn_noisy_combine": ([_P, _P, _I64, _P, _P, _I64, _I64, _I64, _P, _I, _P, _P], _I),
 }
 
 

@@ -15,7 +15,10 @@ them.  The duelling and n-step variants -- DuellingDQNAgent ("duelling_dqn"),
 DuellingDDQNAgent ("duelling_ddqn"), DuellingDDQN_PRBAgent
 ("duelling_ddqn_prb"), DQN_NStep_Agent ("dqn_nstep"), D3QN_PRB_NStep
 ("d3qn_prb_nstep") -- are registered in DQN_VARIANT_AGENTS and take the same
-seat.  Not built: the noisy DQN variants and the human UI.
+seat.  So do the noisy variants -- Noisy_DQN ("noisy_dqn"), Noisy_D3QN
+("noisy_d3qn"), Noisy_D3QN_PRB_NStep ("noisy_d3qn_prb_nstep") -- registered in
+DQN_NOISY_AGENTS: the engine gives every decision its own factorised noise
+(dqn.BatchedDQN.noisy).  Not built: the human UI.
 """
 from .base import Agent
 from .random import DrunkHamster
@@ -24,6 +27,7 @@ from .policy import BatchedReinforceAgent
 from .actor_critic import BatchedACERAgent
 from .dqn import DQNVanilla, DDQNAgent, DQN_PRBAgent, DDQN_PRBAgent
 from .dqn import DuellingDQNAgent, DuellingDDQNAgent, DuellingDDQN_PRBAgent, DQN_NStep_Agent, D3QN_PRB_NStep
+from .dqn import Noisy_DQN, Noisy_D3QN, Noisy_D3QN_PRB_NStep
 
 HUMAN = "human"
 RANDOM_AGENT = "random"
@@ -38,6 +42,9 @@ DUELLING_DDQN = "duelling_ddqn"
 DUELLING_DDQN_PRB = "duelling_ddqn_prb"
 DQN_NSTEP = "dqn_nstep"
 D3QN_PRB_NSTEP = "d3qn_prb_nstep"
+NOISY_DQN = "noisy_dqn"
+NOISY_D3QN = "noisy_d3qn"
+NOISY_D_QN_PRB_NSTEP = "noisy_d3qn_prb_nstep"
 MCS = "mcts"
 PMCS = "pmcs"
 PUCT = "puct"
@@ -64,4 +71,10 @@ DQN_VARIANT_AGENTS = {
     DUELLING_DDQN_PRB: DuellingDDQN_PRBAgent,
     DQN_NSTEP: DQN_NStep_Agent,
     D3QN_PRB_NSTEP: D3QN_PRB_NStep,
+}
+
+DQN_NOISY_AGENTS = {
+    NOISY_DQN: Noisy_DQN,
+    NOISY_D3QN: Noisy_D3QN,
+    NOISY_D_QN_PRB_NSTEP: Noisy_D3QN_PRB_NStep,
 }

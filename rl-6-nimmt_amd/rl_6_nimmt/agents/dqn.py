@@ -1,4 +1,4 @@
-"""Drop-in DQN agents (reference: rl_6_nimmt/agents/dqn.py:42-231,264-436).
+"""Drop-in DQN agents (reference: rl_6_nimmt/agents/dqn.py:42-441).
 
     DQNVanilla     Q(s,a) <- r + gamma * max_a' Q(s',a')
     DDQNAgent      Q(s,a) <- r + gamma * Q_target(s', argmax_a' Q(s',a')), the
@@ -38,7 +38,18 @@ the reference, because seeded sessions depend on it:
   * for n_steps > 1 the row that starts n_steps before the end points at the
     terminal observation with done False, and the target uses gamma ** n_steps
     for the truncated rows as well.
-The noisy variants (Noisy_DQN, Noisy_D3QN, Noisy_D3QN_PRB_NStep) are not built.
+
+    Noisy_DQN, Noisy_D3QN, Noisy_D3QN_PRB_NStep (reference :234-261,404-424,439)
+                   DQNVanilla, DuellingDDQNAgent and D3QN_PRB_NStep on
+                   NoisyFactorizedLinear layers (noisy_init_sigma = 0.5): the
+                   card is the arg-max of the noisy scores over the legal cards
+                   (all 104 when none are given).  No epsilon is used and
+                   Python's `random` is not touched; `info` is {"value": ...};
+                   `eps` is still updated in `learn`.  The noise of a forward
+                   is torch's global generator's: randn for the input buffer,
+                   then for the output buffer, layer after layer, in eval mode
+                   too.  soft_update runs over parameters(): the sigmas follow,
+                   the epsilon buffers do not.
 """
 import math
 import random
@@ -47,7 +58,7 @@ import numpy as np
 import torch
 from torch import nn
 
-from ..utils.nets import DuellingDQNNet, MultiHeadedMLP
+from ..utils.nets import DuellingDQNNet, MultiHeadedMLP, NoisyFactorizedLinear
 from ..utils.replay_buffer import History, PriorityReplayBuffer
 from .base import Agent
 
@@ -58,14 +69,14 @@ def eps_func_decay(episode):
     return max(math.exp(-episode * 0.0025), 0.05)
 
 
-def _q_net(agent, hidden_sizes, activation):
+def _q_net(agent, hidden_sizes, activation, **noisy):
     return MultiHeadedMLP(agent.state_length, hidden_sizes=hidden_sizes, head_sizes=(agent.num_actions,),
-                          activation=activation, head_activations=(None,))
+                          activation=activation, head_activations=(None,), **noisy)
 
 
-def _duelling_net(agent, hidden_sizes, activation):
+def _duelling_net(agent, hidden_sizes, activation, **noisy):
     return DuellingDQNNet(agent.state_length, hidden_sizes=hidden_sizes, out_size=agent.num_actions,
-                          activation=activation)
+                          activation=activation, **noisy)
 
 
 class DQNVanilla(Agent):
@@ -278,4 +289,39 @@ class DuellingDDQN_PRBAgent(DQN_PRBAgent, DuellingDDQNAgent):
 
 
 class D3QN_PRB_NStep(DQN_NStep_Agent, DuellingDDQN_PRBAgent):
+    pass
+
+
+class Noisy_DQN(DQNVanilla):
+    """NoisyNet exploration: every forward of the net draws fresh factorised noise, the card is the arg-max"""
+
+    def __init__(self, *args, noisy_init_sigma=0.5, **kwargs):
+        self.noisy_init_sigma = noisy_init_sigma
+        super().__init__(*args, **kwargs)
+
+    def _setup_networks(self, hidden_sizes, activation):
+        self.dqn_net_local = _q_net(self, hidden_sizes, activation, linear=NoisyFactorizedLinear,
+                                    init_sigma=self.noisy_init_sigma)
+
+    def _action_selection(self, scores, **kwargs):
+        """the best legal card by the noisy scores: no epsilon, no draw from `random`"""
+        legal_actions = kwargs.get("legal_actions", None)
+        actions = np.arange(self.num_actions)
+        q = scores.cpu().numpy()
+        if legal_actions is not None and len(legal_actions) > 0:
+            legal = [int(a) for a in legal_actions]
+            q, actions = q[legal], actions[legal]
+        best = np.argmax(q)
+        return actions[best], {"value": q[best]}
+
+
+class Noisy_D3QN(DuellingDDQNAgent, Noisy_DQN):
+    def _setup_networks(self, hidden_sizes, activation):
+        noisy = dict(linear=NoisyFactorizedLinear, init_sigma=self.noisy_init_sigma)
+        self.dqn_net_local = _duelling_net(self, hidden_sizes, activation, **noisy)
+        self.dqn_net_target = _duelling_net(self, hidden_sizes, activation, **noisy)
+        self.soft_update(self.dqn_net_local, self.dqn_net_target, 1)  # the sigmas too; the epsilon buffers not
+
+
+class Noisy_D3QN_PRB_NStep(Noisy_D3QN, D3QN_PRB_NStep):
     pass

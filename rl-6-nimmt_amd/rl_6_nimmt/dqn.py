@@ -1,8 +1,9 @@
 """Batched DQN family on one MI355X: the engine that seats DQNVanilla,
-DDQNAgent, DQN_PRBAgent, DDQN_PRBAgent and their duelling and n-step
-variants (DuellingDQNAgent, DuellingDDQNAgent, DuellingDDQN_PRBAgent,
-DQN_NStep_Agent, D3QN_PRB_NStep; agents/dqn.py; reference
-agents/dqn.py:42-231,264-436) in the batched league.
+DDQNAgent, DQN_PRBAgent, DDQN_PRBAgent, their duelling and n-step variants
+(DuellingDQNAgent, DuellingDDQNAgent, DuellingDDQN_PRBAgent, DQN_NStep_Agent,
+D3QN_PRB_NStep) and the noisy ones (Noisy_DQN, Noisy_D3QN,
+Noisy_D3QN_PRB_NStep; agents/dqn.py; reference agents/dqn.py:42-441) in the
+batched league.
 
 Every deciding seat of every game acts together.  Per decision batch:
     sn_dqn_obs     the raw _create_states rows (env.py:174-212), as int8 replay
@@ -36,8 +37,19 @@ Different by construction: exploration draws are Philox, not Python's
 `random` (parity unpinned, like the other engines' samplers), a round
 trains on `updates` x `minibatch` rows, not 10 x 64 per game, and the n-step
 targets and losses are fp32 (the reference's are float64: its n-step reward
-is a Python float).  Not built: the noisy variants, and replay inheritance
-for a cloned engine.
+is a Python float).  Not built: replay inheritance for a cloned engine.
+
+A noisy net (utils.nets.NoisyFactorizedLinear layers, plain or duelling:
+`BatchedDQN.noisy`) explores by its noise, and every decision row has its
+own: per layer  y = (x W^T + b) + e_out o ((x o e_in) S^T + s_b)  with the
+row's e_in / e_out from a Philox stream on the device -- sn_noisy_scale, the
+plain GEMM, a sigma GEMM of the same shape, sn_noisy_combine; no effective
+weights are rebuilt.  Selection is the select kernels' greedy branch (eps 0).
+The noise is keyed by (seed, step, global game, seat, layer, side, unit) and
+drawn in training and evaluation alike; `learn` runs the agent's own module
+(one torch.randn sample per minibatch forward, as the reference's _learn).
+`noisy_eps_host` is the float64 model of the noise law, `noisy_forward_host`
+the reference's formula in float64 on given noise rows.
 
 `pack_rows_host`, `unpack_rows_host`, `bellman_target_host`,
 `pack_rows_nstep_host`, `unpack_rows_nstep_host` and `duelling_q_host` are
@@ -45,7 +57,9 @@ the torch models of the kernels (they run on any device); the tests hold the
 kernels to them.
 """
 import copy
+import ctypes
 
+import numpy as np
 import torch
 from torch import nn
 
@@ -172,6 +186,135 @@ def duelling_q_host(V, A):
     return V + (A - A.mean(-1, keepdim=True))
 
 
+# ---------------------------------------------------------------- the noisy nets' device noise (sn_noisy_*)
+NOISY_TAG0 = 0xFFF00
+NOISY_MAX_LAYERS = 64
+_PHILOX_M0, _PHILOX_M1, _PHILOX_W0, _PHILOX_W1 = 0xD2511F53, 0xCD9E8D57, 0x9E3779B9, 0xBB67AE85
+
+
+def noisy_tag(layer, side):
+    """the Philox rollout tag of linear layer `layer` (forward order: the latent layers, then the heads in
+    head_nets order), side 0 = its inputs, 1 = its outputs (SN_NOISY_TAG, include/sechs.h)"""
+    assert 0 <= int(layer) < NOISY_MAX_LAYERS and int(side) in (0, 1)
+    return NOISY_TAG0 + 2 * int(layer) + int(side)
+
+
+def philox4x32_10_host(ctr, key):
+    """Philox4x32-10 on numpy arrays: ctr [..., 4], key [..., 2] (uint32, broadcast together) -> [..., 4] uint32"""
+    ctr, key = np.asarray(ctr, dtype=np.uint64), np.asarray(key, dtype=np.uint64)
+    shape = np.broadcast_shapes(ctr.shape[:-1], key.shape[:-1])
+    c = [np.broadcast_to(ctr[..., j], shape).copy() for j in range(4)]
+    k = [np.broadcast_to(key[..., j], shape).copy() for j in range(2)]
+    mask = np.uint64(0xFFFFFFFF)
+    for _ in range(10):
+        p0, p1 = np.uint64(_PHILOX_M0) * c[0], np.uint64(_PHILOX_M1) * c[2]  # 32 x 32 bits: exact in uint64
+        c = [(p1 >> np.uint64(32)) ^ c[1] ^ k[0], p1 & mask, (p0 >> np.uint64(32)) ^ c[3] ^ k[1], p0 & mask]
+        k = [(k[0] + np.uint64(_PHILOX_W0)) & mask, (k[1] + np.uint64(_PHILOX_W1)) & mask]
+    return np.stack(c, axis=-1).astype(np.uint32)
+
+
+def noisy_normals_host(seed, step, gid, seat, layer, side, width):
+    """the standard normals behind noisy_eps_host, float64 [width]"""
+    seed, pairs = int(seed) & (2**64 - 1), (int(width) + 1) // 2
+    stream = ((int(gid) & 0xFFFFFFFF) << 32) | (int(seat) << 28) | (noisy_tag(layer, side) << 8)
+    ctr = np.zeros((pairs, 4), dtype=np.uint32)
+    ctr[:, 0], ctr[:, 2], ctr[:, 3] = np.arange(pairs), stream & 0xFFFFFFFF, stream >> 32
+    key = np.array([(seed & 0xFFFFFFFF) ^ (int(step) & 0xFFFFFFFF), seed >> 32], dtype=np.uint32)
+    o = philox4x32_10_host(ctr, key).astype(np.float64)
+    u1, u2 = (np.floor(o[:, 0] / 256.0) + 1.0) * 2.0 ** -24, np.floor(o[:, 1] / 256.0) * 2.0 ** -24
+    r = np.sqrt(-2.0 * np.log(u1))
+    n = np.stack((r * np.cos(2.0 * np.pi * u2), r * np.sin(2.0 * np.pi * u2)), axis=1).reshape(-1)
+    return n[: int(width)]
+
+
+def noisy_eps_host(seed, step, gid, seat, layer, side, width):
+    """sn_noisy_eps' law in numpy float64: e = sign(n) sqrt|n| of the units 0 .. width - 1 of decision (global
+    game gid, seat) at decision counter `step`, linear layer `layer`, side 0 (inputs) or 1 (outputs)"""
+    n = noisy_normals_host(seed, step, gid, seat, layer, side, width)
+    return np.sign(n) * np.sqrt(np.abs(n))
+
+
+def noisy_linears(net):
+    """the linear layers of a MultiHeadedMLP (a DuellingDQNNet's `mlp`) in forward order: the latent layers,
+    then the heads in head_nets order -- the order the noise tags count"""
+    mlp = getattr(net, "mlp", net)
+    return [m for m in mlp.latent_net if isinstance(m, nn.Linear)] + [h[0] for h in mlp.head_nets]
+
+
+def noisy_forward_host(net, x, eps):
+    """NoisyFactorizedLinear's formula in float64, row by row: x [n, 47]; eps[l] = (e_in [n, K_l], e_out
+    [n, J_l]), the shaped noise of layer l (noisy_linears order) for every row.  Returns what the module
+    returns: [Q [n, 104]] (a DuellingDQNNet: V + (A - mean A)), as float64 tensors.  ReLU between the latent
+    layers, heads without activation."""
+    mlp = getattr(net, "mlp", net)
+    lin = noisy_linears(net)
+    n_lat = len(lin) - len(mlp.head_nets)
+
+    def layer(l, h):
+        m = lin[l]
+        W, S = m.weight.detach().double().cpu(), m.sigma_weight.detach().double().cpu()
+        b, sb = m.bias.detach().double().cpu(), m.sigma_bias.detach().double().cpu()
+        e_in, e_out = (torch.as_tensor(e, dtype=torch.float64) for e in eps[l])
+        rows = []
+        for r in range(h.shape[0]):
+            Wn = W + S * (e_out[r][:, None] * e_in[r][None, :])
+            rows.append(Wn @ h[r] + b + sb * e_out[r])
+        return torch.stack(rows)
+
+    h = torch.as_tensor(x, dtype=torch.float64).cpu()
+    for l in range(n_lat):
+        h = layer(l, h).clamp_min(0)
+    outs = [layer(n_lat + k, h) for k in range(len(mlp.head_nets))]
+    if hasattr(net, "mlp"):
+        V, A = outs
+        return [V + (A - A.mean(-1, keepdim=True))]
+    return outs
+
+
+class NoisyDeviceNet:
+    """the device form of a noisy Q net: per latent layer (W [J, K], b, S = sigma_weight [J, K] in net_dtype,
+    sigma_bias f32); the heads as one padded GEMM [K, pad] like FusedMLP's, their sigmas block-diagonal
+    [heads * K, pad] (every head scales the latent by its own input noise), sigma_bias f32 [pad];
+    `heads`: (layer index, first column, width) per head in the padded output"""
+
+    def __init__(self, net, duelling, dtype, device):
+        from .utils.nets import NoisyFactorizedLinear
+
+        mlp = net.mlp if duelling else net
+        lat = list(mlp.latent_net)
+        assert all(isinstance(m, NoisyFactorizedLinear) for m in lat[0::2]) and \
+            all(isinstance(m, nn.ReLU) for m in lat[1::2]) and all(len(h) == 1 for h in mlp.head_nets), \
+            "a noisy engine net is NoisyFactorizedLinear / ReLU layers and heads without activation"
+        lin = noisy_linears(net)
+        assert len(lin) <= NOISY_MAX_LAYERS
+        self.layers = []
+        for m in lat[0::2]:
+            w, sg = m.weight.detach(), m.sigma_weight.detach()
+            if w.shape[1] == OBS - 1:  # the 48-wide observation rows go in unsliced
+                w, sg = nn.functional.pad(w, (0, 1)), nn.functional.pad(sg, (0, 1))
+            self.layers.append((w.to(device, dtype).contiguous(), m.bias.detach().to(device, dtype),
+                                sg.to(device, dtype).contiguous(), m.sigma_bias.detach().to(device, torch.float32)))
+        heads = [h[0] for h in mlp.head_nets]
+        n_lat, K, dev = len(self.layers), heads[0].in_features, device
+        order = [1, 0] if duelling else list(range(len(heads)))  # [A | V | pad]: A starts every row aligned
+        total = sum(h.out_features for h in heads)
+        pad = max(16, -(-total // 16) * 16)
+        self.head_w = torch.zeros((K, pad), dtype=dtype, device=dev)
+        self.head_s = torch.zeros((len(heads) * K, pad), dtype=dtype, device=dev)
+        self.head_b = torch.zeros((pad,), dtype=dtype, device=dev)
+        self.head_sb = torch.zeros((pad,), dtype=torch.float32, device=dev)
+        self.heads, c = [None] * len(heads), 0
+        for k in order:
+            h, J = heads[k], heads[k].out_features
+            self.head_w[:, c: c + J] = h.weight.detach().t()
+            self.head_s[k * K: (k + 1) * K, c: c + J] = h.sigma_weight.detach().t()
+            self.head_b[c: c + J], self.head_sb[c: c + J] = h.bias.detach(), h.sigma_bias.detach()
+            self.heads[k] = (n_lat + k, c, J)
+            c += J
+        self.head_sizes = [heads[k].out_features for k in order]
+        self.K, self.pad = K, pad
+
+
 def league_capacity(history_length, seats):
     """replay rows of a league engine: the drop-in's history length and at least two expected rounds of
     transitions (`seats` expected seats of the agent per round, T_STEPS rows each), as a power of two"""
@@ -189,7 +332,7 @@ class BatchedDQN(BatchedEngine):
         DuellingDQNNet as q_net (or target_net): the duelling variants;
         n_steps > 1: the n-step rows and the discount gamma ** n_steps"""
         from .agents.dqn import eps_func_decay
-        from .utils.nets import DuellingDQNNet
+        from .utils.nets import DuellingDQNNet, NoisyFactorizedLinear
 
         super().__init__(env, q_net, seed=seed, seats_mask=seats_mask, net_dtype=net_dtype, max_decisions=max_decisions)
         self.target_net, self.prioritised = target_net, bool(prioritised)
@@ -197,6 +340,8 @@ class BatchedDQN(BatchedEngine):
         self.n_steps = int(n_steps)
         assert self.n_steps >= 1
         self.duelling = isinstance(q_net, DuellingDQNNet)
+        # NoisyFactorizedLinear layers: every decision row draws its own noise on the device, no epsilon
+        self.noisy = any(isinstance(m, NoisyFactorizedLinear) for m in q_net.modules())
         assert target_net is None or isinstance(target_net, DuellingDQNNet) == self.duelling, \
             "the local and the target net are of one kind"
         self.eps_func = eps_func_decay if eps_func is None else eps_func
@@ -221,6 +366,10 @@ class BatchedDQN(BatchedEngine):
         so that A starts every output row 16-byte aligned"""
         version = tuple(p._version for p in self.actor.parameters())
         if self._net is None or version != self._net_version:
+            if self.noisy:
+                self._net = NoisyDeviceNet(self.actor, self.duelling, self.net_dtype, self.env.device)
+                self._net_version = version
+                return self._net
             net = copy.deepcopy(self.actor).to(self.env.device, self.net_dtype)
             net.eval()
             f = FusedMLP.of(net.mlp if self.duelling else net)
@@ -260,7 +409,46 @@ class BatchedDQN(BatchedEngine):
         self.rows_evaluated += states.shape[0]
         return out.float().contiguous()
 
+    def _noisy_values(self, q, states):
+        """a noisy net's padded head output [D, pad] f32 (the plain net: Q in columns 0..103; the duelling
+        net: [A | V | pad]), every row under its own noise of decision counter q.step.  Per layer: x o e_in
+        (sn_noisy_scale), the plain GEMM with bias and the sigma GEMM of the same shape, then mu + e_out o
+        (sg + sigma_b) (sn_noisy_combine; ReLU on the latent layers).  The heads' sigma GEMM is one GEMM over
+        the latent scaled once per head, side by side, against the block-diagonal sigmas."""
+        L, h, st = nat.lib(), self.env._h, self.env._stream()
+        net, D, bf16 = self._net, int(states.shape[0]), int(self.net_dtype == torch.bfloat16)
+        qr = ctypes_ref(q)
+
+        def scale(layer, x, out, col):
+            nat.check(L.sn_noisy_scale(h, qr, noisy_tag(layer, 0), nat.ptr(x), x.stride(0), x.shape[1], bf16,
+                                       ctypes.c_void_p(out.data_ptr() + col * out.element_size()), out.stride(0), st),
+                      "sn_noisy_scale")
+
+        def combine(layer, mu, sg, col0, width, sigma_b, relu):
+            nat.check(L.sn_noisy_combine(h, qr, noisy_tag(layer, 1), nat.ptr(mu), nat.ptr(sg), mu.stride(0), col0, width,
+                                         nat.ptr(sigma_b), relu, nat.ptr(mu), st), "sn_noisy_combine")
+
+        with torch.no_grad():
+            x = states
+            for l, (w, b, s, sb) in enumerate(net.layers):
+                xs = torch.empty_like(x)
+                scale(l, x, xs, 0)
+                mu, sg = torch.addmm(b, x, w.t()).float(), torch.mm(xs, s.t()).float()
+                combine(l, mu, sg, 0, mu.shape[1], sb, 1)
+                x = mu.to(self.net_dtype)
+            K = net.K
+            xs = torch.empty((D, len(net.heads) * K), dtype=self.net_dtype, device=x.device)
+            for k, (layer, _, _) in enumerate(net.heads):
+                scale(layer, x, xs, k * K)
+            mu, sg = torch.addmm(net.head_b, x, net.head_w).float(), torch.mm(xs, net.head_s).float()
+            for layer, col0, width in net.heads:
+                combine(layer, mu, sg, col0, width, net.head_sb, 0)
+        self.rows_evaluated += D
+        return mu
+
     def current_eps(self):
+        if self.noisy:
+            return 0.0  # the noise explores: the select kernels take their greedy branch
         return float(self.eps_func(self.episode)) if self.training else float(self.eps)
 
     # ------------------------------------------------------------ acting
@@ -284,14 +472,16 @@ class BatchedDQN(BatchedEngine):
         states = torch.empty((D, OBS), dtype=self.net_dtype, device=dev)
         nat.check(L.sn_dqn_obs(h, ctypes_ref(q), nat.ptr(obs_t), nat.ptr(states),
                                int(self.net_dtype == torch.bfloat16), st), "sn_dqn_obs")
+        if self.noisy:
+            out = self.q_handed = self._noisy_values(q, states)  # kept: what the select kernel reads
+        else:
+            out = self._head_values(states) if self.duelling else self._q_values(states)
         if self.duelling:
-            heads = self._head_values(states)
-            nat.check(L.sn_dqn_select_duel(h, ctypes_ref(q), nat.ptr(heads), heads.stride(0), NUM_ACTIONS, 0,
+            nat.check(L.sn_dqn_select_duel(h, ctypes_ref(q), nat.ptr(out), out.stride(0), NUM_ACTIONS, 0,
                                            self.eps_used, nat.ptr(self.actions), nat.ptr(self.best_index),
                                            nat.ptr(self.value), st), "sn_dqn_select_duel")
         else:
-            qv = self._q_values(states)
-            nat.check(L.sn_dqn_select(h, ctypes_ref(q), nat.ptr(qv), qv.stride(0), self.eps_used,
+            nat.check(L.sn_dqn_select(h, ctypes_ref(q), nat.ptr(out), out.stride(0), self.eps_used,
                                       nat.ptr(self.actions), nat.ptr(self.best_index), nat.ptr(self.value), st),
                       "sn_dqn_select")
         if record:
@@ -384,12 +574,12 @@ class BatchedDQN(BatchedEngine):
         dev, here = self.actor_device(), self.env.device
         q = self.actor(s.to(dev)[:, : OBS - 1])[0]
         q_eval = q.gather(1, action.to(dev).view(-1, 1)).squeeze(1)
-        with torch.no_grad():
-            qn = self.actor(s2.to(dev)[:, : OBS - 1])[0].to(here).contiguous()
+        with torch.no_grad():  # the drop-in's order of forwards (DDQNAgent._calc_reward): a noisy net draws in each
             qt = None
             if self.target_net is not None:
                 tdev = next(self.target_net.parameters()).device
                 qt = self.target_net(s2.to(tdev)[:, : OBS - 1])[0].to(here).contiguous()
+            qn = self.actor(s2.to(dev)[:, : OBS - 1])[0].to(here).contiguous()
             target = self.bellman_target(qn, qt, reward, not_done).to(dev)
         if self.prioritised:
             weights = batch["weights"].to(dev, torch.float32)

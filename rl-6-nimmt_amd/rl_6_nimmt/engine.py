@@ -12,7 +12,7 @@ from torch import nn
 
 from . import _native as nat
 from .splitk import train_forward
-from .utils.nets import MultiHeadedMLP
+from .utils.nets import MultiHeadedMLP, NoisyFactorizedLinear
 
 ROW = 48
 ctypes_ref = ctypes.byref
@@ -42,9 +42,11 @@ class FusedMLP:
     def of(cls, net):
         lat = list(net.latent_net)
         heads = list(net.head_nets)
-        ok = len(lat) % 2 == 0 and all(isinstance(m, nn.Linear) for m in lat[0::2]) and \
-            all(isinstance(m, nn.ReLU) for m in lat[1::2]) and \
-            all(len(h) == 1 and isinstance(h[0], nn.Linear) for h in heads)
+        def plain(m):  # a NoisyFactorizedLinear is an nn.Linear too: its forward is not W x + b
+            return isinstance(m, nn.Linear) and not isinstance(m, NoisyFactorizedLinear)
+
+        ok = len(lat) % 2 == 0 and all(plain(m) for m in lat[0::2]) and \
+            all(isinstance(m, nn.ReLU) for m in lat[1::2]) and all(len(h) == 1 and plain(h[0]) for h in heads)
         if not ok:
             return cls(net, None, None, None, None)
         layers = [(m.weight.detach(), m.bias.detach()) for m in lat[0::2]]

@@ -18,7 +18,15 @@ Yardsticks:  obs     env.obs() + seat indexing + .float()
              pack_nstep   dqn.pack_rows_nstep_host (n = 3, gamma = 0.99)
 Algorithmic bytes per call: BYTES below.
 
+--noisy: instead, a league round with a Noisy_D3QN_PRB_NStep seat against one
+with a D3QN_PRB_NStep seat (both n_steps = 3; the same slots, seeds and
+opponents): two tournaments in this process, their rounds alternating, the
+phases of every round from device events, medians over `--reps` rounds; then
+the noisy decide's four steps per layer (scale, plain GEMM, sigma GEMM,
+combine) one by one on a decision batch of the league's size.
+
 Usage:  python tools/dqn_prof.py [--reps 30] [--warmup 5] [--no-league] [--slots 65536] [--out dqn_prof.json]
+        python tools/dqn_prof.py --noisy [--reps 10] [--slots 65536] [--out dqn_noisy_prof.json]
 """
 import argparse
 import ctypes
@@ -182,6 +190,101 @@ def league_round(slots, rounds):
     return out
 
 
+def noisy_rounds(slots, reps, warmup):
+    """the noisy seat's round against the plain seat's, rounds alternating"""
+    from rl_6_nimmt.agents import D3QN_PRB_NStep, DrunkHamster, Noisy_D3QN_PRB_NStep
+    from rl_6_nimmt.league import BatchedTournament
+
+    seats = {"noisy": Noisy_D3QN_PRB_NStep, "plain": D3QN_PRB_NStep}
+    leagues = {}
+    for key, cls in seats.items():
+        torch.manual_seed(0)
+        t = BatchedTournament(slots, 2, 4, seed=1, train=True, fused=False)
+        for name, agent in (("R0", DrunkHamster()), ("R1", DrunkHamster()), ("Q", cls(history_length=1000, n_steps=3)),
+                            ("R2", DrunkHamster())):
+            t.add_player(name, agent)
+        t.play_games(1)  # warm-up: allocations, the first GEMM plans, the optimiser state
+        t.phase_timing = True
+        leagues[key] = t
+    rounds = {key: [] for key in seats}
+    for r in range(warmup + reps):
+        for key in (("noisy", "plain") if r % 2 == 0 else ("plain", "noisy")):
+            t = leagues[key]
+            t.phase_ms, t.phase_host_ms = {}, {}
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            t.play_games(1)
+            b.record()
+            b.synchronize()
+            if r >= warmup:
+                rounds[key].append(dict(t.phase_ms, round=a.elapsed_time(b)))
+    out = {"slots": slots, "reps": reps, "net_dtype": str(leagues["noisy"].net_dtype)}
+    for key, t in leagues.items():
+        eng = t.engines["Q"]
+        phases = {k: [r[k] for r in rounds[key]] for k in rounds[key][0]}
+        out[key] = {"agent": seats[key].__name__,
+                    "phase_ms": {k: {"median": statistics.median(v), "min": min(v), "max": max(v)} for k, v in phases.items()},
+                    "deciders_last_round": int(eng.D), "minibatch": eng.minibatch, "updates": eng.updates,
+                    "pipe_errors": t.env.pipe_errors()}
+        t.close()
+    dec = {key: out[key]["phase_ms"]["decide Q"]["median"] for key in seats}
+    out["decide_ms_noisy_over_plain"] = dec["noisy"] / dec["plain"]
+    return out
+
+
+def noisy_steps(deciders, reps, warmup, dtype=torch.bfloat16):
+    """the four steps of every layer of a noisy duelling decide, each timed on its own (us, medians)"""
+    from rl_6_nimmt import _native as nat
+    from rl_6_nimmt.dqn import BatchedDQN, noisy_tag
+    from rl_6_nimmt.utils.nets import DuellingDQNNet, NoisyFactorizedLinear
+    from rl_6_nimmt.vec_env import VecSechsNimmtEnv
+
+    games = deciders // SEATS
+    env = VecSechsNimmtEnv(games, SEATS, seed=1)
+    dev = env.device
+    env.reset()
+    torch.manual_seed(0)
+    net = DuellingDQNNet(47, (64,), 104, torch.nn.ReLU(), linear=NoisyFactorizedLinear, init_sigma=0.5).to(dev)
+    eng = BatchedDQN(env, net, capacity=1 << 10, net_dtype=dtype)
+    dn, n = eng.sync_net(), games * SEATS
+    L, st, q = nat.lib(), env._stream(), eng._params(10)
+    ref, bf16 = ctypes.byref(q), int(dtype == torch.bfloat16)
+    x = torch.randn((n, 48), device=dev).to(dtype)
+    w, b, sg_w, sb = dn.layers[0]
+    xs, mu32, sg32 = torch.empty_like(x), torch.randn((n, 64), device=dev), torch.randn((n, 64), device=dev)
+    h = torch.randn((n, 64), device=dev).to(dtype)
+    hs = torch.empty((n, 128), dtype=dtype, device=dev)
+    hmu, hsg = torch.randn((n, 112), device=dev), torch.randn((n, 112), device=dev)
+
+    def scale(layer, src, dst, col):
+        nat.check(L.sn_noisy_scale(env._h, ref, noisy_tag(layer, 0), nat.ptr(src), src.stride(0), src.shape[1], bf16,
+                                   ctypes.c_void_p(dst.data_ptr() + col * dst.element_size()), dst.stride(0), st),
+                  "sn_noisy_scale")
+
+    def combine(layer, mu, sg, col0, width, sigma_b, relu):
+        nat.check(L.sn_noisy_combine(env._h, ref, noisy_tag(layer, 1), nat.ptr(mu), nat.ptr(sg), mu.stride(0), col0, width,
+                                     nat.ptr(sigma_b), relu, nat.ptr(mu), st), "sn_noisy_combine")
+
+    legs = {"latent scale": lambda: scale(0, x, xs, 0),
+            "latent GEMM (+ .float())": lambda: torch.addmm(b, x, w.t()).float(),
+            "latent sigma GEMM (+ .float())": lambda: torch.mm(xs, sg_w.t()).float(),
+            "latent combine (+ cast back)": lambda: (combine(0, mu32, sg32, 0, 64, sb, 1), mu32.to(dtype)),
+            "heads scale (V and A)": lambda: (scale(1, h, hs, 0), scale(2, h, hs, 64)),
+            "heads GEMM (+ .float())": lambda: torch.addmm(dn.head_b, h, dn.head_w).float(),
+            "heads sigma GEMM (+ .float())": lambda: torch.mm(hs, dn.head_s).float(),
+            "heads combine (V and A)": lambda: (combine(1, hmu, hsg, 104, 1, dn.head_sb, 0),
+                                                combine(2, hmu, hsg, 0, 104, dn.head_sb, 0)),
+            "plain latent GEMM (bias + ReLU fused)": lambda: torch._addmm_activation(b, x, w.t())}
+    times = {k: [] for k in legs}
+    for r in range(warmup + reps):
+        for k, fn in legs.items():
+            t = timed(fn)
+            if r >= warmup:
+                times[k].append(t)
+    return {"deciders": n, "net_dtype": str(dtype),
+            "us": {k: {"median": statistics.median(v), "min": min(v), "max": max(v)} for k, v in times.items()}}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=30)
@@ -190,9 +293,20 @@ def main():
     ap.add_argument("--slots", type=int, default=65536)
     ap.add_argument("--rounds", type=int, default=2)
     ap.add_argument("--out", default="")
+    ap.add_argument("--noisy", action="store_true")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("dqn_prof: no GPU -- times are taken on the device or not at all")
+    if args.noisy:
+        result = {"league": noisy_rounds(args.slots, args.reps, args.warmup)}
+        result["steps"] = noisy_steps(result["league"]["noisy"]["deciders_last_round"] // SEATS * SEATS or SEATS,
+                                      max(args.reps, 20), args.warmup)
+        text = json.dumps(result, indent=1)
+        print(text)
+        if args.out:
+            with open(args.out, "w") as f:
+                f.write(text + "\n")
+        return
     legs, keep = kernel_legs()
     result = {"deciders": D, "episode_rows": T * D, "minibatch": MINIBATCH, "capacity": CAPACITY, "reps": args.reps,
               "bytes": BYTES}

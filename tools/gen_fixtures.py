@@ -73,6 +73,13 @@ Fixture families (SURVEY.md §4 "What the build must add"):
                            sessions also reject seeds whose importance
                            weights hinge on a near-zero TD error
                            (DQNVAR_MIN_LEAF)
+  F18 dqn_noisy_games.json  the same recipe for Noisy_DQN, Noisy_D3QN and
+      dqn_noisy_weights.npz   Noisy_D3QN_PRB_NStep(n_steps=3), one session
+                           each: per step the move and info["value"] (no
+                           epsilon), the losses, the PER indices, the weights
+                           without the epsilon buffers; the gap of a decision
+                           is taken over scores[legal].  torch's CPU generator
+                           drives the weights and every noise draw
 
 F15 / F16 pin the reference's *Python* semantics of the prioritised replay:
 with the stand-in numba.jit the sampler `_get_leaf_ids` runs as plain Python
@@ -1275,6 +1282,121 @@ def gen_dqnvar(ref, out):
                    "sessions": sessions}, f)
 
 
+# ----------------------------------------------------------------------------
+# F18: the noisy DQN agents in training sessions
+# ----------------------------------------------------------------------------
+DQNNOISY_CLASSES = [("Noisy_DQN", {}), ("Noisy_D3QN", {}), ("Noisy_D3QN_PRB_NStep", {"n_steps": 3})]
+
+
+def _noisy_session(cls_name, seed, extra_kw):
+    """_dqn_session for the noisy agents: info has no "eps" and the scores are not masked in place, so the gap is
+    taken between the two best of scores[legal]; the same rejection rules.  torch's CPU generator drives the
+    initial weights and every noise draw."""
+    import random
+
+    import torch
+    from rl_6_nimmt import agents as A
+    from rl_6_nimmt.play import GameSession
+
+    torch.manual_seed(seed)
+    kw = dict(DQN_KW, **extra_kw)
+    ag = getattr(A, cls_name)(**kw)
+    agents = [ag] + [A.DrunkHamster() for _ in range(3)]
+    ag.train()
+
+    def weights():  # the epsilon buffers are redrawn by every forward: not part of the record
+        return {k: v.detach().numpy().astype(np.float32).copy() for k, v in ag.state_dict().items()
+                if ".epsilon_" not in k}
+
+    init = weights()
+    tr = {"steps": [], "losses": [], "per_idx": []}
+    worst = {"gap": float("inf"), "margin": float("inf"), "leaf": float("inf")}
+    sel, lrn = ag._action_selection, ag.learn
+
+    def sel_rec(scores, **k):
+        act, info = sel(scores, **k)
+        assert set(info) == {"value"}
+        top = np.sort(scores.numpy()[list(k["legal_actions"])])[::-1]
+        if len(top) > 1:
+            worst["gap"] = min(worst["gap"], float(top[0] - top[1]))
+        tr["steps"].append([int(act), float(info["value"])])
+        return act, info
+
+    def lrn_rec(*a, **k):
+        loss = lrn(*a, **k)
+        tr["losses"].append(float(loss[0]))
+        return loss
+
+    ag._action_selection, ag.learn = sel_rec, lrn_rec
+    prb = "PRB" in cls_name
+    if prb:
+        buf = ag.history
+        smp = buf.sample
+
+        def smp_rec(n):
+            first = len(buf.tree.tree) - buf.tree.capacity
+            worst["leaf"] = min(worst["leaf"], float(np.min(buf.tree.tree[first: first + buf.tree.num_items])))
+            res, us, margin, _ = _recorded_sample(buf, n, smp)
+            worst["margin"] = min(worst["margin"], margin)
+            tr["per_idx"].append([int(x) for x in res[0]])
+            return res
+
+        buf.sample = smp_rec
+    np.random.seed(seed)
+    random.seed(seed)
+    sess = GameSession(*agents)
+    for _ in range(DQN_GAMES):
+        sess.play_game()
+    if worst["gap"] < DQN_GAP or worst["margin"] < DQN_MARGIN or (prb and worst["leaf"] < DQNVAR_MIN_LEAF):
+        return None
+    final = weights()
+    rec = {"agent": cls_name, "seed": seed, "games": DQN_GAMES, "kwargs": kw, "results": [[int(x) for x in r] for r in sess.results],
+           "min_gap": worst["gap"]}
+    if prb:
+        rec.update(beta=float(ag.history.beta), total_priority=float(ag.history.tree.total_priority),
+                   len=len(ag.history), min_margin=worst["margin"], min_leaf=worst["leaf"])
+    series = {"actions": np.array([s[0] for s in tr["steps"]], dtype=np.int64),
+              "values": np.array([s[1] for s in tr["steps"]]), "losses": np.array(tr["losses"])}
+    if prb:
+        series["per_idx"] = np.array(tr["per_idx"], dtype=np.int64)
+    return rec, init, final, series
+
+
+def gen_dqnnoisy(ref, out):
+    sessions, arrays = [], {}
+    for ci, (cls_name, extra) in enumerate(DQNNOISY_CLASSES):
+        seed = 10 * ci
+        while True:
+            got = _noisy_session(cls_name, seed, extra)
+            if got is not None:
+                break
+            seed += 100  # rejected, by the F16 rules or DQNVAR_MIN_LEAF
+        rec, init, final, series = got
+        si = len(sessions)
+        for k, v in series.items():
+            arrays[f"s{si}_{k}"] = v
+        for k, v in init.items():
+            if k.startswith("dqn_net_target."):  # the local net's copy (soft_update with tau = 1): not stored
+                assert np.array_equal(v, init[k.replace("dqn_net_target.", "dqn_net_local.", 1)])
+                continue
+            arrays[f"s{si}_init_{k}"] = v
+        for k, v in final.items():
+            arrays[f"s{si}_final_{k}"] = v
+        sessions.append(rec)
+    np.savez_compressed(os.path.join(out, "dqn_noisy_weights.npz"), **arrays)
+    with open(os.path.join(out, "dqn_noisy_games.json"), "w") as f:
+        json.dump({"protocol": "dqn_games.json's protocol for Noisy_DQN, Noisy_D3QN and Noisy_D3QN_PRB_NStep (kwargs holds "
+                               "n_steps; no eps_func): torch.manual_seed(seed) drives the initial weights and every noise "
+                               "draw of the session.  dqn_noisy_weights.npz: s<i>_actions / _values = the move and "
+                               "info.value of every forward (info has no eps), s<i>_losses, s<i>_per_idx (the "
+                               "prioritised session), s<i>_init_* / s<i>_final_* = agent.state_dict() without the "
+                               "epsilon_input / epsilon_output buffers and without s<i>_init_dqn_net_target.* (equal to "
+                               "s<i>_init_dqn_net_local.*).  Rejected seeds: a decision whose two best of scores[legal] "
+                               "are within 1e-3 (min_gap), a PER descent within 1e-6 x total of a threshold "
+                               "(min_margin), a smallest held leaf below 0.15 at any sample (min_leaf)",
+                   "sessions": sessions}, f)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests", "golden"))
@@ -1299,6 +1421,7 @@ def main():
         ("per", gen_per),
         ("dqn", gen_dqn),
         ("dqnvar", gen_dqnvar),
+        ("dqnnoisy", gen_dqnnoisy),
     ]
     for name, fn in steps:
         if args.only and name not in args.only.split(","):
