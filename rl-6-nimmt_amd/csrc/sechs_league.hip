@@ -14,7 +14,7 @@
 //     draw (golden F11 "dropin" leagues);
 //   * external agents (the net agents: PUCTAgent, PUCTCustomedAgent,
 //     BatchedACERAgent): their batched engines chose the card beforehand
-//     (sechs_puct.hip over the handle's decision lists); it is checked
+//     (sechs_puct.hip / sechs_agents.hip over the handle's decision lists); it is checked
 //     against the hand like env.py:114-118.
 // A game that ends writes its record (seats word, results); the next game of
 // every slot starts with sn_reset (the seat draw, then the deal: the next

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""The batched DQN kernels (sn_dqn_* in csrc/sechs_puct.hip, sn_per_gather in
+"""The batched DQN kernels (sn_dqn_* in csrc/sechs_agents.hip, sn_per_gather in
 csrc/sechs_replay.hip) against their PyTorch-ROCm forms on the same inputs,
 and one league round with a DDQN_PRBAgent seat by phase.
 
