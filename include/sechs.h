@@ -405,13 +405,22 @@ sn_status sn_mcs_choose(sn_env* env, const int32_t* sums, int32_t* actions, void
 sn_status sn_mcs_play_exact(sn_env* env, uint32_t mcs_seats, int mc_per_card, int mc_max, int32_t* actions,
                             int32_t* rewards, int32_t* status, void* stream);
 
-/* Reference-exact MCSAgent._mcts for D independent decisions (one lane
-   each), for the drop-in agent.  Device buffers: board [D][4][6] int8 (-1
-   pad), hand [D][10] int8 (the legal actions, -1 pad), avail [D][4] uint32
-   card memory, mt_keys [D][624] + mt_pos [D]: numpy-form MT19937 states
-   (np.random.get_state()[1:3]) advanced in place.  actions [D] int32: the
-   chosen card, or -(card)-2 when quirk Q6 applies; sums / counts [D][10]
-   (optional) = per-move playout sums and counts. */
+/* Reference-exact MCSAgent._mcts for D independent decisions (one wave
+   each), for the drop-in agent; num_players K in 1..10.  Device buffers:
+   board [D][4][6] int8 (-1 pad), hand [D][10] int8 (the legal actions, -1
+   pad), avail [D][4] uint32 card memory, mt_keys [D][624] + mt_pos [D]:
+   numpy-form MT19937 states (np.random.get_state()[1:3]) advanced in place.
+   actions [D] int32: the chosen card, or -(card)-2 when quirk Q6 applies;
+   sums / counts [D][10] (optional) = per-move playout sums and counts.
+   A hand of one card is played without a search: sums / counts 0, the state
+   untouched.
+   Preconditions per decision, on the caller's buffers: a hand of n >= 1
+   cards; for n >= 2 a card memory of A cards with max(2, (K - 1) n) <= A <=
+   104 (every playout deals the K - 1 opponents n cards each from it); 0 <=
+   mt_pos.  A decision that breaks one gets actions[d] = -1, zeroed sums /
+   counts, and its (key, pos) left as they were (the reference raises there:
+   np.random.choice on an empty hand); the other decisions of the launch are
+   not affected. */
 sn_status sn_mcs_decide_exact(int device, int64_t num_decisions, int num_players, const int8_t* board,
                               const int8_t* hand, const uint32_t* avail, int mc_per_card, int mc_max,
                               uint32_t* mt_keys, int32_t* mt_pos, int32_t* actions, int32_t* sums, int32_t* counts,

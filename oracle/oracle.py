@@ -109,6 +109,10 @@ def lib():
         L.or_vec_scores.argtypes = [ctypes.POINTER(_Vec), P]
         L.or_mcs_game.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_uint32, P, P]
         L.or_mcs_game.restype = ctypes.c_int
+        L.or_rng_set_mt.argtypes = [ctypes.POINTER(_Rng), P, ctypes.c_int]
+        L.or_mcs_decide.argtypes = [P, P, ctypes.c_int, P, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                    ctypes.POINTER(_Rng), P, P, P]
+        L.or_mcs_decide.restype = ctypes.c_int
         _lib = L
     return _lib
 
@@ -125,6 +129,20 @@ class Rng:
             lib().or_rng_init_mt(ctypes.byref(self.s), seed & 0xFFFFFFFF)
         else:
             lib().or_rng_init_philox(ctypes.byref(self.s), seed, stream)
+
+    @classmethod
+    def from_numpy(cls, key, pos):
+        """the stream of np.random.RandomState.get_state()[1:3]"""
+        r = cls.__new__(cls)
+        r.s = _Rng()
+        k = np.ascontiguousarray(key, dtype=np.uint32)
+        assert k.shape == (624,)
+        lib().or_rng_set_mt(ctypes.byref(r.s), _p(k), int(pos))
+        return r
+
+    @property
+    def pos(self):
+        return int(self.s.pos)
 
     def next(self):
         return lib().or_rng_next(ctypes.byref(self.s))
@@ -277,6 +295,39 @@ def mcs_game(seats, mc_per_card, mc_max, seed):
     r = np.zeros((10, n), dtype=np.int32)
     rc = lib().or_mcs_game(seats.encode(), n, mc_per_card, mc_max, seed & 0xFFFFFFFF, _p(a), _p(r))
     return rc, a, r
+
+
+def mcs_decide(board, hand, avail, num_players, mc_per_card, mc_max, key, pos):
+    """One MCSAgent decision (mcts.py:91-172) on the numpy stream (key, pos):
+    board = the rows' card lists, hand = the legal cards, avail = the card
+    memory.  Returns (card, q6, sums[10], counts[10], key', pos'); card is -1
+    and the stream untouched where the memory cannot deal the opponents."""
+    b = np.full((ROWS, THRESHOLD), -1, dtype=np.int64)
+    for r, row in enumerate(board):
+        b[r, : len(row)] = row
+    h = np.ascontiguousarray(sorted(int(c) for c in hand), dtype=np.int32)
+    a = np.ascontiguousarray(sorted(int(c) for c in avail), dtype=np.int32)
+    rng = Rng.from_numpy(key, pos)
+    q6 = ctypes.c_int(0)
+    sums = np.zeros(HAND, dtype=np.int32)
+    counts = np.zeros(HAND, dtype=np.int32)
+    card = lib().or_mcs_decide(_p(b), _p(h), len(h), _p(a), len(a), num_players, mc_per_card, mc_max,
+                               ctypes.byref(rng.s), ctypes.addressof(q6), _p(sums), _p(counts))
+    return card, bool(q6.value), sums, counts, rng.key, rng.pos
+
+
+def mcs_position(num_players, n, seed):
+    """A position for seat 0 to decide at a hand of n cards: an oracle game
+    dealt and played with uniform moves on Rng(seed), seat 0's card memory
+    kept from the deal on.  Returns (board rows, hand, memory)."""
+    rng = Rng(RNG_NUMPY_MT, seed)
+    g = Game(num_players)
+    g.reset(rng)
+    mem = mcs_memorize([], g, 0)
+    while len(g.hands[0]) > n:
+        g.step([g.random_action(rng, p) for p in range(num_players)])
+        mem = mcs_memorize(mem, g, 0)
+    return g.board, g.hands[0], mem
 
 
 def mcs_memorize(avail, game, seat, mcs_cards=104):

@@ -29,6 +29,14 @@ void or_rng_init_mt(or_rng* r, uint32_t seed) {
     r->pos = MT_N;
 }
 
+void or_rng_set_mt(or_rng* r, const uint32_t* key, int pos) {
+    /* RandomState.set_state(('MT19937', key, pos)) */
+    memset(r, 0, sizeof(*r));
+    r->mode = OR_RNG_NUMPY_MT;
+    memcpy(r->mt, key, sizeof(r->mt));
+    r->pos = pos;
+}
+
 static void mt_twist(uint32_t* mt) {
     for (int i = 0; i < MT_N; i++) {
         uint32_t y = (mt[i] & 0x80000000u) | (mt[(i + 1) % MT_N] & 0x7fffffffu);
@@ -406,28 +414,18 @@ static long long factorial_capped(int n, long long cap) {
     return f;
 }
 
-static int mcs_forward_q6(or_mcs* m, or_rng* r, const int64_t* state, int include_summaries, const int* legal, int n,
-                          int* q6) {
-    const int L = or_obs_len(include_summaries);
-    const int64_t* board = state + L - OR_ROWS * OR_THRESHOLD; /* _board_from_state: state[-24:] (mcts.py:75-85) */
-    if (n == OR_HAND) {                                          /* _initialize_game (mcts.py:62-64) */
-        m->n_avail = OR_MAX_CARDS;
-        for (int i = 0; i < OR_MAX_CARDS; i++) m->avail[i] = i;
-        m->num_players = (int)state[10];
-    }
-    /* _memorize_cards (mcts.py:66-73): legal + flattened board, negatives skipped */
-    for (int i = 0; i < n; i++) avail_remove(m, legal[i]);
-    for (int i = 0; i < OR_ROWS * OR_THRESHOLD; i++)
-        if (board[i] >= 0) avail_remove(m, (int)board[i]);
-    if (n == 1) return legal[0]; /* mcts.py:52-53 */
-
+/* _mcts + _choose_action_from_outcomes (mcts.py:91-172) for a hand of n >= 2
+   cards on the memory m->avail, board = the 24 board cells of the state
+   (-1 pad).  sum / cnt [OR_HAND]: the per-move outcome sums (outcomes are
+   integers) and playout counts. */
+static int mcs_search(const or_mcs* m, or_rng* r, const int64_t* board, const int* legal, int n, int32_t* sum,
+                      int32_t* cnt, int* q6) {
     /* _mcts (mcts.py:91-103), n_mc = min(mc_max, mc_per_card * n!) (:105-106) */
     long long cap = m->mc_max;
     long long f = factorial_capped(n, cap);
     long long n_mc = (long long)m->mc_per_card * f;
     if (n_mc > cap) n_mc = cap;
-    double sum[OR_HAND] = {0};
-    int cnt[OR_HAND] = {0};
+    for (int i = 0; i < OR_HAND; i++) sum[i] = 0, cnt[i] = 0;
     const int N = m->num_players;
     for (long long it = 0; it < n_mc; it++) {
         /* _draw_env + _deal_hands (mcts.py:108-127) */
@@ -452,7 +450,7 @@ static int mcs_forward_q6(or_mcs* m, or_rng* r, const int64_t* state, int includ
         }
         /* _play_out (mcts.py:129-154) with MCSAgent._choose_action_mc uniform (:187-188) */
         int first = -1;
-        double outcome = 0.0;
+        int32_t outcome = 0;
         while (!or_is_done(&g)) {
             int a[OR_MAX_PLAYERS];
             int32_t rw[OR_MAX_PLAYERS];
@@ -475,10 +473,45 @@ static int mcs_forward_q6(or_mcs* m, or_rng* r, const int64_t* state, int includ
             *q6 = 1;
             continue;
         }
-        double mean = sum[i] / (double)cnt[i];
+        double mean = (double)sum[i] / (double)cnt[i];
         if (mean > best_mean) best_mean = mean, best = legal[i];
     }
     return best;
+}
+
+static int mcs_forward_q6(or_mcs* m, or_rng* r, const int64_t* state, int include_summaries, const int* legal, int n,
+                          int* q6) {
+    const int L = or_obs_len(include_summaries);
+    const int64_t* board = state + L - OR_ROWS * OR_THRESHOLD; /* _board_from_state: state[-24:] (mcts.py:75-85) */
+    if (n == OR_HAND) {                                          /* _initialize_game (mcts.py:62-64) */
+        m->n_avail = OR_MAX_CARDS;
+        for (int i = 0; i < OR_MAX_CARDS; i++) m->avail[i] = i;
+        m->num_players = (int)state[10];
+    }
+    /* _memorize_cards (mcts.py:66-73): legal + flattened board, negatives skipped */
+    for (int i = 0; i < n; i++) avail_remove(m, legal[i]);
+    for (int i = 0; i < OR_ROWS * OR_THRESHOLD; i++)
+        if (board[i] >= 0) avail_remove(m, (int)board[i]);
+    if (n == 1) return legal[0]; /* mcts.py:52-53 */
+    int32_t sum[OR_HAND], cnt[OR_HAND];
+    return mcs_search(m, r, board, legal, n, sum, cnt, q6);
+}
+
+int or_mcs_decide(const int64_t* board, const int* legal, int n, const int* avail, int n_avail, int num_players,
+                  int mc_per_card, int mc_max, or_rng* r, int* q6, int32_t* sums, int32_t* counts) {
+    *q6 = 0;
+    for (int i = 0; i < OR_HAND; i++) sums[i] = 0, counts[i] = 0;
+    if (n < 1 || n > OR_HAND || n_avail < 0 || n_avail > OR_MAX_CARDS) return -1;
+    if (n == 1) return legal[0]; /* mcts.py:52-53 */
+    /* the deal takes (num_players - 1) * n cards: with fewer the reference
+       raises (np.random.choice on an empty hand) */
+    if (n_avail < (num_players - 1) * n || n_avail < 2) return -1;
+    or_mcs m;
+    or_mcs_init(&m, mc_per_card, mc_max);
+    m.num_players = num_players;
+    m.n_avail = n_avail;
+    for (int i = 0; i < n_avail; i++) m.avail[i] = avail[i];
+    return mcs_search(&m, r, board, legal, n, sums, counts, q6);
 }
 
 int or_mcs_forward(or_mcs* m, or_rng* r, const int64_t* state, int include_summaries, const int* legal, int n) {

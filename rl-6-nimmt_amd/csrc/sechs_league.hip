@@ -157,7 +157,7 @@ __global__ __launch_bounds__(kBlock) void k_league_step(DevState s, LeagueStepAr
 // cards to lpc for k_league_step, which then resolves the step.
 template <int N>
 __global__ __launch_bounds__(64) void k_league_mcs(DevState s, LeagueStepArgs a) {
-    __shared__ WmcsLds L;
+    __shared__ WmcsLds<kWmMaxP> L;  // k <= 6 seats
     const int64_t g = blockIdx.x;
     const uint32_t lane = threadIdx.x;
     const uint32_t lg = s.lgs[g], k = lg & 15u;

@@ -218,21 +218,42 @@ struct DecideArgs {
 // MCSAgent decisions (sn_mcs_decide_exact), one wave each (sechs_mcs_wave.h):
 // the numpy key and pos in LDS, the playouts' draws decoded 64 words per instruction and
 // played 64 at a time in the lanes; same words, same order, same outputs.
+// The draw buffer holds wm_max_p(N) draws per playout, the most any card
+// memory of <= 104 cards asks for.  A decision whose inputs break the
+// preconditions (sechs.h) answers -1 and leaves its stream alone; the test is
+// uniform over the decision's one-wave workgroup.
 template <int N>
 __global__ __launch_bounds__(64) void k_mcs_decide_wave(DecideArgs a) {
-    __shared__ WmcsLds L;
+    __shared__ WmcsLds<wm_max_p(N)> L;
     __shared__ uint32_t head[64];
     const int64_t d = blockIdx.x;
     const uint32_t lane = threadIdx.x;
     uint32_t* key = a.mt_keys + d * kMtN;
-    WaveMt m{L.st, L.stage, 0u, 0u, 0u, 0u, false, head};
-    wmt_load(m, key, mt_code_from_numpy(a.mt_pos[d]), lane);
+    int32_t* sums = a.sums ? a.sums + d * kHand : nullptr;
+    int32_t* counts = a.counts ? a.counts + d * kHand : nullptr;
     u32x4 hs = {0u, 0u, 0u, 0u};
     for (int k = 0; k < kHand; k++) {
         const int c = a.hand[d * kHand + k];
         if (c >= 0) hs = set_bit(hs, (uint32_t)c);
     }
     const Hand me = hand_from_set(hs);
+    const uint32_t n = hand_len(me);
+    const u32x4 av = {a.avail[d * 4 + 0], a.avail[d * 4 + 1], a.avail[d * 4 + 2], a.avail[d * 4 + 3]};
+    const uint32_t A = set_count(av);
+    const int32_t pos0 = a.mt_pos[d];
+    // a search deals (N - 1) n cards from the memory; one card is played
+    // without a search (mcts.py:52-53) and nothing is drawn
+    const bool searchable = A >= max(2u, (uint32_t)(N - 1) * n) && A <= (uint32_t)kMaxCards && pos0 >= 0;
+    if (n <= 1u || !searchable) {
+        if (lane < (uint32_t)kHand) {
+            if (sums) sums[lane] = 0;
+            if (counts) counts[lane] = 0;
+        }
+        if (lane == 0u) a.actions[d] = (n == 1u) ? (int32_t)hand_get(me, 0u) : -1;
+        return;
+    }
+    WaveMt m{L.st, L.stage, 0u, 0u, 0u, 0u, false, head};
+    wmt_load(m, key, mt_code_from_numpy(pos0), lane);
     uint32_t lo[4], hi[4];
 #pragma unroll
     for (int r = 0; r < kRows; r++) {
@@ -251,18 +272,8 @@ __global__ __launch_bounds__(64) void k_mcs_decide_wave(DecideArgs a) {
     Board b;
     b.lo = u32x4{lo[0], lo[1], lo[2], lo[3]};
     b.hi = u32x4{hi[0], hi[1], hi[2], hi[3]};
-    const u32x4 av = {a.avail[d * 4 + 0], a.avail[d * 4 + 1], a.avail[d * 4 + 2], a.avail[d * 4 + 3]};
-    const uint32_t n = hand_len(me);
     bool q6 = false;
-    uint32_t c = hand_get(me, 0u);
-    int32_t* sums = a.sums ? a.sums + d * kHand : nullptr;
-    int32_t* counts = a.counts ? a.counts + d * kHand : nullptr;
-    if (n > 1u) {
-        c = wmcs_decide<N>(m, L, b, me, n, av, a.mc_per_card, a.mc_max, &q6, lane, sums, counts);
-    } else if (lane < (uint32_t)kHand) {
-        if (sums) sums[lane] = 0;
-        if (counts) counts[lane] = 0;
-    }
+    const uint32_t c = wmcs_decide<N>(m, L, b, me, n, av, a.mc_per_card, a.mc_max, &q6, lane, sums, counts);
     const int32_t pos = wmt_store_numpy(m, key, lane);
     if (lane == 0u) {
         a.actions[d] = q6 ? -(int32_t)c - 2 : (int32_t)c;  // -(card)-2 flags quirk Q6

@@ -23,7 +23,12 @@
 namespace sechs {
 
 constexpr uint32_t kWmStage = 1024;  // tempered low bytes staged ahead of the decoder (ring)
-constexpr uint32_t kWmMaxP = 160;    // draws per playout: (A - 1) + k (n - 1) <= 102 + 6 * 9
+// draws per playout: P = (A - 1) + k (n - 1), at most 103 + 9 k for a card
+// memory of A <= 104 cards and a hand of n <= 10.  The draw buffer is sized
+// from this bound at compile time (WmcsLds<MaxP>), so no accepted input can
+// overrun it.
+constexpr uint32_t wm_max_p(int k) { return 103u + 9u * (uint32_t)k; }
+constexpr uint32_t kWmMaxP = 160;  // the league's buffer, k <= 6: wm_max_p(6) = 157, rounded up
 
 // a numpy MT19937 stream owned by one wave: state code semantics as MtGen
 // (sechs_device.h: slots [0, T) hold this round, [T, 624) the previous one;
@@ -137,10 +142,13 @@ __device__ __forceinline__ void wmt_store(const WaveMt& m, uint32_t* gst, uint32
 // export in numpy's (key, pos) form: a consumer still in the previous round
 // (the stream ran at most one 64-word chunk into the next) gets that round's
 // key back from the saved head; otherwise the current round is finished in
-// place, as numpy twists whole blocks (mt_export, sechs_mcs.hip)
+// place, as numpy twists whole blocks (mt_export, sechs_mcs.hip).  A consumer
+// that stopped on the previous round's last word is still in it: numpy twists
+// on the next draw, so its state is that round's key at pos 624, not the next
+// round's at pos 0 (u == T, which only the first chunk of a round can leave).
 __device__ __forceinline__ int32_t wmt_store_numpy(WaveMt& m, uint32_t* key, uint32_t lane) {
-    const uint32_t u = m.wr - m.rd;  // staged, unconsumed
-    if (m.head && u > m.T) {         // straddle: T <= 64
+    const uint32_t u = m.wr - m.rd;            // staged, unconsumed
+    if (m.head && m.T <= 64u && u >= m.T) {  // straddle
         for (uint32_t i = lane; i < (uint32_t)kMtN; i += 64u) key[i] = (i < m.T) ? m.head[i] : m.st[i];
         return (int32_t)(kMtN - (u - m.T));
     }
@@ -196,11 +204,13 @@ __device__ __forceinline__ void wmcs_playout(const uint8_t* d, uint32_t A, uint3
     }
 }
 
-// LDS a decision wave needs
+// LDS a decision wave needs; MaxP >= wm_max_p(K) of every K decided on it
+template <uint32_t MaxP>
 struct WmcsLds {
+    static constexpr uint32_t kMaxP = MaxP;
     uint32_t st[kMtN];
     uint8_t stage[kWmStage];
-    uint8_t dr[64 * kWmMaxP];
+    uint8_t dr[64 * MaxP];
     uint8_t deck[64 * kDeckStride];
     uint8_t sorted[kDeckStride];
 };
@@ -212,10 +222,14 @@ struct WmcsLds {
 // memory and the hands then stay in registers -- 225 -> 138 VGPRs, league MCS
 // step 164 -> 106 ms per run.py round; the one-decision drop-in kernel keeps
 // the out-of-line form, wmcs_decide below)
-template <int K>
-__device__ __forceinline__ uint32_t wmcs_decide_inl(WaveMt& m, WmcsLds& L, const Board& root, const Hand& me, uint32_t n,
+// Precondition (the caller's to check): max(2, (K - 1) n) <= A <= 104 for the
+// A cards of `avail` -- the deal reads (K - 1) n deck slots, A - 1 must not
+// wrap, and P >= 2 keeps `magic` in 32 bits.
+template <int K, class Lds>
+__device__ __forceinline__ uint32_t wmcs_decide_inl(WaveMt& m, Lds& L, const Board& root, const Hand& me, uint32_t n,
                                                     u32x4 avail, int mc_per_card, int mc_max, bool* q6, uint32_t lane,
                                                     int32_t* sums_out = nullptr, int32_t* counts_out = nullptr) {
+    static_assert(Lds::kMaxP >= wm_max_p(K), "draw buffer smaller than a playout's draws");
     int64_t fact = 1;
     for (uint32_t i = 2; i <= n; i++) fact *= i;
     const uint32_t n_mc = (uint32_t)min((int64_t)mc_max, (int64_t)mc_per_card * fact);
@@ -283,8 +297,8 @@ __device__ __forceinline__ uint32_t wmcs_decide_inl(WaveMt& m, WmcsLds& L, const
     return hand_get(me, best);
 }
 
-template <int K>
-__device__ uint32_t wmcs_decide(WaveMt& m, WmcsLds& L, const Board& root, const Hand& me, uint32_t n, u32x4 avail,
+template <int K, class Lds>
+__device__ uint32_t wmcs_decide(WaveMt& m, Lds& L, const Board& root, const Hand& me, uint32_t n, u32x4 avail,
                                 int mc_per_card, int mc_max, bool* q6, uint32_t lane, int32_t* sums_out = nullptr,
                                 int32_t* counts_out = nullptr) {
     return wmcs_decide_inl<K>(m, L, root, me, n, avail, mc_per_card, mc_max, q6, lane, sums_out, counts_out);

@@ -109,6 +109,9 @@ class MCSAgent(BaseMCAgent):
         key = d_key.cpu().numpy().view(np.uint32)[0].copy()
         np.random.set_state((st[0], key, int(d_pos.item()), st[3], st[4]))
         act = int(d_act.item())
+        if act == -1:  # the reference raises too: np.random.choice on an opponent's empty hand
+            raise ValueError(f"MCS: a card memory of {len(self.available_cards)} cards cannot deal "
+                             f"{self.num_players - 1} opponents {len(legal_actions)} cards each")
         if act < 0:
             act = -act - 2
             logger.warning("MCS: a legal move got no playout (the reference raises IndexError here, quirk Q6)")

@@ -58,12 +58,34 @@ def test_play_exact_batch_matches_oracle():
         assert np.array_equal(acts[:, g], a) and np.array_equal(rews[:, g], r), g
 
 
+def test_play_exact_batch_matches_oracle_7_seats():
+    """the lane form above four seats: a few 7-player games, mc_max = 30"""
+    from rl_6_nimmt.mcs import play_exact
+    from rl_6_nimmt.vec_env import VecSechsNimmtEnv
+
+    B, seats, base = 6, "MRRMRRR", 2280  # seeds picked so that three games are whole and three raise
+    env = VecSechsNimmtEnv(B, 7, seed=base, rng="numpy")
+    acts, rews, status = play_exact(env, seats, 10, 30)
+    acts, rews, status = acts.cpu().numpy(), rews.cpu().numpy(), status.cpu().numpy()
+    whole = 0
+    for g in range(B):
+        rc, a, r = O.mcs_game(seats, 10, 30, base + g)
+        # the oracle stops where the reference raises (Q6); the device plays on:
+        # the steps before that one are the same game
+        steps = int((a != 0).any(axis=1).sum())
+        assert steps == 10 if rc == 0 else (rc == -2 and steps < 10)
+        whole += rc == 0
+        assert status[g] == (0 if rc == 0 else 1), g
+        assert np.array_equal(acts[:steps, g], a[:steps]) and np.array_equal(rews[:steps, g], r[:steps]), g
+    assert whole == 3
+
+
 def test_dropin_mcs_agent_in_game_session():
     from rl_6_nimmt import GameSession
     from rl_6_nimmt.agents import DrunkHamster, MCSAgent
 
     for g in load("mcs_games.json")["games"]:
-        if "error" in g or g["mc_max"] > 100:
+        if "error" in g:
             continue
         agents = [MCSAgent(mc_max=g["mc_max"], mc_per_card=g["mc_per_card"]) if c == "M" else DrunkHamster() for c in g["seats"]]
         np.random.seed(g["seed"])
@@ -109,6 +131,62 @@ def test_stratified_engine_matches_oracle(N):
                 assert acts[g, p] == G.hands[p][best]
         rew, done, inv = env.step(torch.from_numpy(acts))
         assert (inv.cpu().numpy() == -1).all()
+
+
+@pytest.mark.parametrize("N", [3, 10])
+@pytest.mark.parametrize("R", [128, 192, 512])
+def test_stratified_launch_shapes_match_oracle(N, R):
+    """The launch shapes the other tests never take: one block of 128 or 192
+    playouts (2 or 3 waves in the block sum) and R = 512, two blocks per move
+    adding into sums by atomics (blockIdx.z > 0), with the per-playout output
+    of sn_mcs_rollouts_ex.  Two decision steps of B = 4 games: sums bit for
+    bit against the oracle, the playouts add up to the sums, and the first 64
+    playouts are those of R = 64 (the stream is keyed by the playout index)."""
+    from concurrent.futures import ThreadPoolExecutor
+
+    from rl_6_nimmt import _native as nat
+    from rl_6_nimmt.mcs import BatchedMCS
+    from rl_6_nimmt.vec_env import VecSechsNimmtEnv
+
+    B, seed = 4, 0xFACADE
+    D = B * N
+    env = VecSechsNimmtEnv(B, N, seed=11, rng="philox", game_offset=3)
+    env.reset()
+    mcs = BatchedMCS(env, rollouts=R, seed=seed)
+    L, h, st = nat.lib(), env._h, env._stream()
+    sums64 = torch.zeros((D, 10), dtype=torch.int32, device=env.device)
+    po = torch.zeros((D, 10, R), dtype=torch.int32, device=env.device)
+    po64 = torch.zeros((D, 10, 64), dtype=torch.int32, device=env.device)
+    mem = [[[] for _ in range(N)] for _ in range(B)]
+    pool = ThreadPoolExecutor(max_workers=min(16, os.cpu_count() or 1))
+    for step in range(2):
+        board, hands = env.board().cpu().numpy(), env.hands().cpu().numpy()
+        po.zero_(), po64.zero_()
+        nat.check(L.sn_mcs_memorize(h, nat.ptr(mcs.avail), 104, st), "sn_mcs_memorize")
+        nat.check(L.sn_mcs_rollouts_ex(h, nat.ptr(mcs.avail), 64, seed, step, nat.ptr(sums64), nat.ptr(po64), st),
+                  "sn_mcs_rollouts_ex")
+        nat.check(L.sn_mcs_rollouts_ex(h, nat.ptr(mcs.avail), R, seed, step, nat.ptr(mcs.sums), nat.ptr(po), st),
+                  "sn_mcs_rollouts_ex")
+        nat.check(L.sn_mcs_choose(h, nat.ptr(mcs.sums), nat.ptr(mcs.actions), st), "sn_mcs_choose")
+        sums, p, p64 = mcs.sums.cpu().numpy(), po.cpu().numpy(), po64.cpu().numpy()
+        games = [_oracle_game(board[g], hands[g], N) for g in range(B)]
+        for g in range(B):
+            for q in range(N):
+                mem[g][q] = O.mcs_memorize(mem[g][q], games[g], q)
+
+        def one(gq):
+            g, q = gq
+            return O.mcs_stratified(games[g], q, mem[g][q], R, seed, step, 3 + g)
+
+        refs = list(pool.map(one, [(g, q) for g in range(B) for q in range(N)]))
+        for d, ref in enumerate(refs):
+            assert np.array_equal(sums[d], ref), (step, d)
+        assert np.array_equal(p.sum(-1), sums)
+        assert np.array_equal(p[:, :, :64], p64)
+        assert np.array_equal(p64.sum(-1), sums64.cpu().numpy())
+        rew, done, inv = env.step(mcs.actions.cpu())
+        assert (inv.cpu().numpy() == -1).all()
+    pool.shutdown()
 
 
 def test_stratified_engine_matches_oracle_at_bench_rollouts():
