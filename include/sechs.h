@@ -272,7 +272,7 @@ sn_status sn_debug_puct_phases(uint64_t* out, int n);
    ptend[slot] (B words), 2 = decode-ahead record slot (kDecQuads x B 16-B
    pieces, piece-major).  No pipeline state is changed. */
 sn_status sn_debug_pipe_words(sn_env* env, int what, int slot, uint32_t* out);
-/* Device-side invariant checks (SN_DASSERT in sechs_device.h / sechs_env.hip:
+/* Device-side invariant checks (SN_DASSERT in sechs_env.hip and its headers:
    a played card is in its seat's hand, the cards of a step are distinct, a
    card goes to a row ending below it (or undercuts), rows hold 1..5 cards,
    a deal gives ten distinct cards per hand): violations counted since the

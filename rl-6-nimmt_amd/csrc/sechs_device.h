@@ -25,8 +25,8 @@ typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 // SECHS_DEBUG (the libsechs_debug.so variant, make libsechs_debug.so):
 // SN_DASSERT counts violated invariants of the game engine in a device word
 // (sn_debug_failures reads and clears it) instead of trapping -- a trap on a
-// shared GPU box can take the queue down.  Active in sechs_env.hip's kernels
-// (SECHS_DEBUG_HERE); a no-op in the product library and in the other files.
+// shared GPU box can take the queue down.  Active in the kernels of sechs_env.hip
+// and the headers it includes (SECHS_DEBUG_HERE); a no-op in the product library and in the other files.
 #if defined(SECHS_DEBUG) && defined(SECHS_DEBUG_HERE)
 __device__ unsigned int g_sn_dbg[2] = {0u, 0xFFFFFFFFu};  // failures, first failing line
 #define SN_DASSERT(c)                                                   \

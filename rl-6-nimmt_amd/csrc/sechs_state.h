@@ -43,7 +43,7 @@ struct DevState {
     u32x4* ring;     // [ring_w/16][B] low bytes of the words k_mt_prep twisted ahead
     int ring_w;      // ring words per game (multiple of 64), 0 = no ring
     int pad2_;
-    // pipelined twist-ahead (k_mt_ahead / RingPipe, sechs_env.hip):
+    // pipelined twist-ahead (k_mt_ahead, sechs_mt_ahead.h / RingPipe below):
     u32x4* pring;    // [kPipeRing/64][B] 64-B chunks: byte of absolute stream word p at p mod kPipeRing (ring_byte)
     uint32_t* pabsc; // [kPipeSlots][B] consumer position after a play launch (by launch index mod kPipeSlots)
     uint32_t* ptend; // [kPipeSlots][B] end of the twisted words after a prep launch (the same)
@@ -65,7 +65,7 @@ constexpr int kMt0Levels = 16;   // word-0 crossings kept in mt0: the rounds the
 constexpr int kPipeSlots = 8;    // pabsc buffers (by play launch index mod 8; ptend uses 2, by twist parity)
 constexpr int kDecSlot = kPipeSlots;  // pabsc slots kDecSlot + (G & 1): the decoder's position after decode G
 constexpr int kDecRecords = 16;  // decode-ahead record ring (episodes; >= 2K + 2 for K <= 5)
-constexpr int kDecQuads = 6;     // 16-B pieces per record (24 dwords, the layout at DecSrc)
+constexpr int kDecQuads = 6;     // 16-B pieces per record (24 dwords, the layout at DecSrc, sechs_decode.h)
 constexpr int kTimingEvents = 6; // SN_OPT_TIMING events per launch: play, twist, decode (start, end)
 constexpr int kPipeRing = 8192;  // ring bytes per game (a power of two >= kPipeSpanMax + a 64-B chunk, below)
 
@@ -611,6 +611,37 @@ __device__ __forceinline__ void store_game(const DevState& s, int64_t g, const G
     }
     s.row_lo[0 * B + g] = G.b.lo.x, s.row_lo[1 * B + g] = G.b.lo.y, s.row_lo[2 * B + g] = G.b.lo.z, s.row_lo[3 * B + g] = G.b.lo.w;
     s.row_hi[0 * B + g] = G.b.hi.x, s.row_hi[1 * B + g] = G.b.hi.y, s.row_hi[2 * B + g] = G.b.hi.z, s.row_hi[3 * B + g] = G.b.hi.w;
+}
+
+// A dealt game as packed words, the form in which a producer hands the next deal to the play waves: seat p's sorted
+// legal list as hw[3p .. 3p + 2] = lo32, hi32, hi (bytes 8, 9 | 0xFFFF0000), env.py:104-107, and the four row cards
+// r0..r3 as the bytes of the returned word, env.py:108-110.  k_decode packs its records with it and DecSrc::deal
+// installs them.  (k_play_split's `dealt` columns hold the same words, written out by hand there: through these
+// helpers the compiler rescheduled that kernel and it measured 0.8 % slower.)
+template <int N>
+__device__ __forceinline__ uint32_t pack_deal(const Game<N>& G, uint32_t* hw) {
+#pragma unroll
+    for (int p = 0; p < N; p++) {
+        hw[3 * p] = (uint32_t)G.hand[p].lo;
+        hw[3 * p + 1] = (uint32_t)(G.hand[p].lo >> 32);
+        hw[3 * p + 2] = G.hand[p].hi;
+    }
+    return G.b.lo.x | (G.b.lo.y << 8) | (G.b.lo.z << 16) | (G.b.lo.w << 24);
+}
+
+// ... and back: the game as dealt (scores 0, kHand cards a seat, one card a row)
+template <int N>
+__device__ __forceinline__ void install_deal(const uint32_t* hw, uint32_t rows, Game<N>& G) {
+#pragma unroll
+    for (int p = 0; p < N; p++) {
+        G.hand[p].lo = (uint64_t)hw[3 * p] | ((uint64_t)hw[3 * p + 1] << 32);
+        G.hand[p].hi = hw[3 * p + 2];
+        G.score[p] = 0;
+    }
+    const uint32_t r0 = rows & 0xFFu, r1 = (rows >> 8) & 0xFFu, r2 = (rows >> 16) & 0xFFu, r3 = rows >> 24;
+    G.b.lo = u32x4{r0, r1, r2, r3};
+    G.b.hi = u32x4{meta_row(r0), meta_row(r1), meta_row(r2), meta_row(r3)};
+    G.n = kHand;
 }
 
 // 10-input sorting network: 29 compare-exchanges in 8 layers (Knuth, TAOCP

@@ -185,6 +185,17 @@ class VecSechsNimmtEnv:
         nat.check(nat.lib().sn_clear_results(self._h, self._stream()), "sn_clear_results")
 
     # ------------------------------------------------------------ numpy RNG bridge
+    # set_option's keywords in their order of application: (keyword, SN_OPT_*, conversion)
+    _OPTIONS = (
+        ("pipe_lead", nat.SN_OPT_PIPE_LEAD, int), ("pipe_gpw", nat.SN_OPT_PIPE_GPW, int),
+        ("play_split", nat.SN_OPT_PLAY_SPLIT, int), ("twist_every", nat.SN_OPT_TWIST_EVERY, int),
+        ("twist_round", nat.SN_OPT_TWIST_ROUND, int), ("twist_depth", nat.SN_OPT_TWIST_DEPTH, int),
+        ("play_group", nat.SN_OPT_PLAY_GROUP, int), ("walk_draws", nat.SN_OPT_DEC_WALK, int),
+        ("pipe_dec", nat.SN_OPT_PIPE_DEC, int), ("twist_skip", nat.SN_OPT_TWIST_SKIP, int),
+        ("pipeline", nat.SN_OPT_PIPELINE, lambda v: int(bool(v))), ("ring_words", nat.SN_OPT_RING_WORDS, int),
+        ("chunk_steps", nat.SN_OPT_CHUNK_STEPS, int),
+    )
+
     def set_option(self, ring_words=None, chunk_steps=None, pipeline=None, pipe_gpw=None, pipe_lead=None,
                    play_split=None, twist_round=None, twist_every=None, twist_skip=None, pipe_dec=None,
                    twist_depth=None, play_group=None, walk_draws=None):
@@ -197,32 +208,10 @@ class VecSechsNimmtEnv:
         window position (1) or through the byte buffer (0)); results never
         depend on it (except the test knobs pipe_lead < 600 and twist_skip = 1, which make
         overruns -- PipeOverrunError -- likely / certain)"""
-        if pipe_lead is not None:
-            nat.check(nat.lib().sn_set_option(self._h, nat.SN_OPT_PIPE_LEAD, int(pipe_lead)), "sn_set_option")
-        if pipe_gpw is not None:
-            nat.check(nat.lib().sn_set_option(self._h, nat.SN_OPT_PIPE_GPW, int(pipe_gpw)), "sn_set_option")
-        if play_split is not None:
-            nat.check(nat.lib().sn_set_option(self._h, nat.SN_OPT_PLAY_SPLIT, int(play_split)), "sn_set_option")
-        if twist_every is not None:
-            nat.check(nat.lib().sn_set_option(self._h, nat.SN_OPT_TWIST_EVERY, int(twist_every)), "sn_set_option")
-        if twist_round is not None:
-            nat.check(nat.lib().sn_set_option(self._h, nat.SN_OPT_TWIST_ROUND, int(twist_round)), "sn_set_option")
-        if twist_depth is not None:
-            nat.check(nat.lib().sn_set_option(self._h, nat.SN_OPT_TWIST_DEPTH, int(twist_depth)), "sn_set_option")
-        if play_group is not None:
-            nat.check(nat.lib().sn_set_option(self._h, nat.SN_OPT_PLAY_GROUP, int(play_group)), "sn_set_option")
-        if walk_draws is not None:
-            nat.check(nat.lib().sn_set_option(self._h, nat.SN_OPT_DEC_WALK, int(walk_draws)), "sn_set_option")
-        if pipe_dec is not None:
-            nat.check(nat.lib().sn_set_option(self._h, nat.SN_OPT_PIPE_DEC, int(pipe_dec)), "sn_set_option")
-        if twist_skip is not None:
-            nat.check(nat.lib().sn_set_option(self._h, nat.SN_OPT_TWIST_SKIP, int(twist_skip)), "sn_set_option")
-        if pipeline is not None:
-            nat.check(nat.lib().sn_set_option(self._h, nat.SN_OPT_PIPELINE, int(bool(pipeline))), "sn_set_option")
-        if ring_words is not None:
-            nat.check(nat.lib().sn_set_option(self._h, nat.SN_OPT_RING_WORDS, int(ring_words)), "sn_set_option")
-        if chunk_steps is not None:
-            nat.check(nat.lib().sn_set_option(self._h, nat.SN_OPT_CHUNK_STEPS, int(chunk_steps)), "sn_set_option")
+        given = locals()
+        for name, opt, conv in self._OPTIONS:
+            if given[name] is not None:
+                nat.check(nat.lib().sn_set_option(self._h, opt, conv(given[name])), "sn_set_option")
 
     def time_kernels(self, launches):
         """record HIP events around the next `launches` pipelined k_play /

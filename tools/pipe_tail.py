@@ -8,7 +8,7 @@ DrunkHamster self-play draws: the deal, np.random.shuffle(arange(104)) =
 random_interval(i) for i = 103..1 (env.py:99-112), and per env-step each
 seat's legal[random_interval(n - 1)] for n = 10..1 (agents/random.py:9).
 k_mt_ahead keeps 593..600 words twisted past the consumer position of the
-launch before the running one (sechs_env.hip), so a launch PAIR must draw
+launch before the running one (sechs_mt_ahead.h), so a launch PAIR must draw
 <= 592 words.  A pair of 10-step launches = two episodes' draws; a pair of
 5-step launches = at most one episode's (10 consecutive steps hold one deal
 and every hand size once).  This prints P(words > 592) per game and launch
