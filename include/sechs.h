@@ -454,7 +454,12 @@ sn_status sn_mcs_decide_exact(int device, int64_t num_decisions, int num_players
      sn_puct_choose      stats (n > 1)
    They may all be NULL for sn_puct_root_rows, sn_pcv_choose,
    sn_policy_sample and sn_dqn_* (those kernels take only the deciding seats,
-   n, seed and step from this struct). */
+   n, seed and step from this struct).
+   A rollout number is the 20-bit tag of its Philox streams, and the tags from
+   0xFFF00 up belong to the draws outside a rollout (SN_NOISY_TAG, the
+   epsilon-greedy draws, the policy sample): sn_puct_deal and sn_puct_step
+   (`rollout`), sn_puct_deal_batch and sn_puct_rollouts (r0 + nr - 1) return
+   SN_EINVAL and launch nothing when a rollout number reaches 0xFFF00. */
 typedef struct {
     uint32_t seats_mask;   /* deciding seats (bit p = seat p) */
     int n;                 /* hand size at the root (all games in lockstep) */

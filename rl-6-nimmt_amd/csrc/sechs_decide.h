@@ -64,7 +64,7 @@ constexpr uint32_t kNoisyTag0 = 0xFFF00u;    // + 2 * layer + side: a noisy laye
 constexpr uint32_t kNoisyLayers = 64u;
 constexpr uint32_t kSelectTag = 0xFFFFEu;    // the epsilon-greedy draws (k_dqn_select, k_dqn_select_duel)
 constexpr uint32_t kSampleTag = 0xFFFFFu;    // the policy sample (k_policy_sample)
-constexpr uint32_t kRolloutTagEnd = kNoisyTag0;  // a rollout number stays below this (nothing refuses a larger one)
+constexpr uint32_t kRolloutTagEnd = kNoisyTag0;  // a rollout number stays below this (rollout_tags_ok: the search refuses a larger one)
 static_assert(kRolloutTagEnd <= kNoisyTag0 && kNoisyTag0 + 2u * kNoisyLayers <= kSelectTag && kSelectTag < kSampleTag &&
                   kSampleTag < (1u << 20),
               "rollout numbers, then the noise tags, the select tag, the sample tag: disjoint 20-bit ranges in this order");
@@ -134,6 +134,15 @@ inline sn_status puct_need(const sn_puct* q, unsigned need) {
     for (const auto& f : fields)
         if ((need & f.bit) && !f.p)
             return set_error(SN_EINVAL, std::string("sn_puct.") + f.name + " is NULL: this call reads or writes it");
+    return SN_OK;
+}
+
+// rollouts r0 .. r0 + nr - 1 are stream tags: one at or past kRolloutTagEnd would draw from the stream of a
+// noise, select or sample tag, so the entry points that deal or step a rollout refuse it before they launch
+inline sn_status rollout_tags_ok(int64_t r0, int64_t nr, const char* what) {
+    if (r0 + nr > (int64_t)kRolloutTagEnd)
+        return set_error(SN_EINVAL, std::string(what) + ": rollout number " + std::to_string(r0 + nr - 1) +
+                                        " reaches the reserved stream tags (rollouts stay below 0xFFF00)");
     return SN_OK;
 }
 

@@ -1167,6 +1167,7 @@ sn_status sn_puct_deal(sn_env* e, const sn_puct* q, void* stream) {
     PuctArgs a{};
     sn_status st = puct_args(e, q, a, kNeedAvail | kNeedRo);
     if (st != SN_OK) return st;
+    if ((st = rollout_tags_ok(q->rollout, 1, "sn_puct_deal")) != SN_OK) return st;
     hipStream_t s = (hipStream_t)stream;
     SN_DISPATCH_N(e->s.N, hipLaunchKernelGGL((k_puct_deal<NN>), dim3(grid_for(a.D)), dim3(kBlock), 0, s, e->s, a));
     HIP_TRY(hipGetLastError());
@@ -1178,6 +1179,7 @@ sn_status sn_puct_deal_batch(sn_env* e, const sn_puct* q, int r0, int nr, void* 
     sn_status st = puct_args(e, q, a, kNeedAvail);
     if (st != SN_OK) return st;
     if (r0 < 0 || nr < 1 || !ro_out) return set_error(SN_EINVAL, "need r0 >= 0, nr >= 1 and an output buffer");
+    if ((st = rollout_tags_ok(r0, nr, "sn_puct_deal_batch")) != SN_OK) return st;
     hipStream_t s = (hipStream_t)stream;
     const int64_t lanes = a.D * nr;
     SN_DISPATCH_N(e->s.N, hipLaunchKernelGGL((k_puct_deal_batch<NN>), dim3(grid_for(lanes)), dim3(kBlock), 0, s, e->s, a,
@@ -1207,6 +1209,7 @@ sn_status sn_puct_step(sn_env* e, const sn_puct* q, const float* logits, int t, 
     sn_status st = puct_args(e, q, a, kNeedRo | kNeedStats | kNeedHist | kNeedProbs);
     if (st != SN_OK) return st;
     if (n_cur < 1 || n_cur > a.n || t < 0 || t + n_cur != a.n) return set_error(SN_EINVAL, "t / n_cur inconsistent");
+    if ((st = rollout_tags_ok(q->rollout, 1, "sn_puct_step")) != SN_OK) return st;
     hipStream_t s = (hipStream_t)stream;
     const int ls = q->logit_stride > 1 ? q->logit_stride : 1;
     const char* sv = getenv("SECHS_PUCT_STEP_SEATS");  // "0": the one-lane-per-decision kernel (A/B, tests)
@@ -1275,6 +1278,7 @@ sn_status sn_puct_rollouts(sn_env* e, const sn_puct* q, int r0, int nr, void* ro
     sn_status st = puct_args(e, q, a, kNeedStats | kNeedHist | kNeedProbs);
     if (st != SN_OK) return st;
     if (r0 < 0 || nr < 1 || !ro_base) return set_error(SN_EINVAL, "need r0 >= 0, nr >= 1 and the dealt states");
+    if ((st = rollout_tags_ok(r0, nr, "sn_puct_rollouts")) != SN_OK) return st;
     if (!w1s || !w1c || !w2 || !head) return set_error(SN_EINVAL, "NULL argument");
     if ((((uintptr_t)w1s) | ((uintptr_t)w2) | ((uintptr_t)w1c) | ((uintptr_t)head)) & 15)
         return set_error(SN_EINVAL, "w1s / w2 / w1c / head must be 16-B aligned");

@@ -64,7 +64,8 @@ import torch
 from torch import nn
 
 from . import _native as nat
-from .engine import BatchedEngine, FusedMLP, ctypes_ref
+from .engine import (BatchedEngine, FusedMLP, ctypes_ref, decision_words_host,
+                     philox4x32_10_host)  # noqa: F401  (philox4x32_10_host: re-exported)
 from .replay import DevicePER
 
 T_STEPS = 10
@@ -189,7 +190,6 @@ def duelling_q_host(V, A):
 # ---------------------------------------------------------------- the noisy nets' device noise (sn_noisy_*)
 NOISY_TAG0 = 0xFFF00
 NOISY_MAX_LAYERS = 64
-_PHILOX_M0, _PHILOX_M1, _PHILOX_W0, _PHILOX_W1 = 0xD2511F53, 0xCD9E8D57, 0x9E3779B9, 0xBB67AE85
 
 
 def noisy_tag(layer, side):
@@ -199,28 +199,11 @@ def noisy_tag(layer, side):
     return NOISY_TAG0 + 2 * int(layer) + int(side)
 
 
-def philox4x32_10_host(ctr, key):
-    """Philox4x32-10 on numpy arrays: ctr [..., 4], key [..., 2] (uint32, broadcast together) -> [..., 4] uint32"""
-    ctr, key = np.asarray(ctr, dtype=np.uint64), np.asarray(key, dtype=np.uint64)
-    shape = np.broadcast_shapes(ctr.shape[:-1], key.shape[:-1])
-    c = [np.broadcast_to(ctr[..., j], shape).copy() for j in range(4)]
-    k = [np.broadcast_to(key[..., j], shape).copy() for j in range(2)]
-    mask = np.uint64(0xFFFFFFFF)
-    for _ in range(10):
-        p0, p1 = np.uint64(_PHILOX_M0) * c[0], np.uint64(_PHILOX_M1) * c[2]  # 32 x 32 bits: exact in uint64
-        c = [(p1 >> np.uint64(32)) ^ c[1] ^ k[0], p1 & mask, (p0 >> np.uint64(32)) ^ c[3] ^ k[1], p0 & mask]
-        k = [(k[0] + np.uint64(_PHILOX_W0)) & mask, (k[1] + np.uint64(_PHILOX_W1)) & mask]
-    return np.stack(c, axis=-1).astype(np.uint32)
-
-
 def noisy_normals_host(seed, step, gid, seat, layer, side, width):
     """the standard normals behind noisy_eps_host, float64 [width]"""
-    seed, pairs = int(seed) & (2**64 - 1), (int(width) + 1) // 2
-    stream = ((int(gid) & 0xFFFFFFFF) << 32) | (int(seat) << 28) | (noisy_tag(layer, side) << 8)
-    ctr = np.zeros((pairs, 4), dtype=np.uint32)
-    ctr[:, 0], ctr[:, 2], ctr[:, 3] = np.arange(pairs), stream & 0xFFFFFFFF, stream >> 32
-    key = np.array([(seed & 0xFFFFFFFF) ^ (int(step) & 0xFFFFFFFF), seed >> 32], dtype=np.uint32)
-    o = philox4x32_10_host(ctr, key).astype(np.float64)
+    pairs = (int(width) + 1) // 2
+    o = decision_words_host(seed, step, int(gid), int(seat), noisy_tag(layer, side), 0, np.arange(pairs))
+    o = o.astype(np.float64)
     u1, u2 = (np.floor(o[:, 0] / 256.0) + 1.0) * 2.0 ** -24, np.floor(o[:, 1] / 256.0) * 2.0 ** -24
     r = np.sqrt(-2.0 * np.log(u1))
     n = np.stack((r * np.cos(2.0 * np.pi * u2), r * np.sin(2.0 * np.pi * u2)), axis=1).reshape(-1)

@@ -7,6 +7,7 @@ leaves them NULL (include/sechs.h, at sn_puct, lists the calls that need them)."
 import copy
 import ctypes
 
+import numpy as np
 import torch
 from torch import nn
 
@@ -16,6 +17,49 @@ from .utils.nets import MultiHeadedMLP, NoisyFactorizedLinear
 
 ROW = 48
 ctypes_ref = ctypes.byref
+
+# ---------------------------------------------------------------- the decisions' Philox streams, on the host
+# Every random word a kernel draws for a decision is Philox4x32-10 keyed (seed lo ^ step, seed hi) at the counter
+# (c, 0, stream lo, stream hi); the stream word and its reserved tags are csrc/sechs_decide.h's (dec_stream).  This
+# is the format's one host owner: the models the kernels are tested against are built on it.
+SELECT_TAG = 0xFFFFE       # the epsilon-greedy draws (sn_dqn_select, sn_dqn_select_duel)
+SAMPLE_TAG = 0xFFFFF       # the policy sample (sn_policy_sample)
+ROLLOUT_TAG_END = 0xFFF00  # a PUCT rollout's tag is its number, below this; the noisy layers' tags start here
+_PHILOX_M0, _PHILOX_M1, _PHILOX_W0, _PHILOX_W1 = 0xD2511F53, 0xCD9E8D57, 0x9E3779B9, 0xBB67AE85
+_U32 = np.uint64(0xFFFFFFFF)
+
+
+def philox4x32_10_host(ctr, key):
+    """Philox4x32-10 on numpy arrays: ctr [..., 4], key [..., 2] (uint32, broadcast together) -> [..., 4] uint32"""
+    ctr, key = np.asarray(ctr, dtype=np.uint64), np.asarray(key, dtype=np.uint64)
+    shape = np.broadcast_shapes(ctr.shape[:-1], key.shape[:-1])
+    c = [np.broadcast_to(ctr[..., j], shape).copy() for j in range(4)]
+    k = [np.broadcast_to(key[..., j], shape).copy() for j in range(2)]
+    for _ in range(10):
+        p0, p1 = np.uint64(_PHILOX_M0) * c[0], np.uint64(_PHILOX_M1) * c[2]  # 32 x 32 bits: exact in uint64
+        c = [(p1 >> np.uint64(32)) ^ c[1] ^ k[0], p1 & _U32, (p0 >> np.uint64(32)) ^ c[3] ^ k[1], p0 & _U32]
+        k = [(k[0] + np.uint64(_PHILOX_W0)) & _U32, (k[1] + np.uint64(_PHILOX_W1)) & _U32]
+    return np.stack(c, axis=-1).astype(np.uint32)
+
+
+def dec_stream_host(gid, seat, tag, low=0):
+    """dec_stream's word as uint64: (gid's low 32 bits) << 32 | seat << 28 | tag << 8 | low byte.  gid is the
+    global game id, game_offset + g; seat < 16, tag < 2**20 and low < 256 keep the fields apart.  The arguments
+    broadcast together."""
+    gid, seat, tag, low = (np.asarray(v, dtype=np.uint64) for v in (gid, seat, tag, low))
+    assert bool((seat < 16).all()) and bool((tag < (1 << 20)).all()) and bool((low < 256).all())
+    return ((gid & _U32) << np.uint64(32)) | (seat << np.uint64(28)) | (tag << np.uint64(8)) | low
+
+
+def decision_words_host(seed, step, gid, seat, tag, low, counters):
+    """the four Philox words of every (decision, counter): uint32 [..., 4] over gid, seat and counters broadcast
+    together.  seed: the engine's 64-bit seed, step: its 32-bit decision counter (sn_puct.seed / .step)."""
+    seed = int(seed) & (2**64 - 1)
+    stream, counters = dec_stream_host(gid, seat, tag, low), np.asarray(counters, dtype=np.uint64)
+    ctr = np.zeros(np.broadcast_shapes(stream.shape, counters.shape) + (4,), dtype=np.uint64)
+    ctr[..., 0], ctr[..., 2], ctr[..., 3] = counters & _U32, stream & _U32, stream >> np.uint64(32)
+    key = np.array([(seed & 0xFFFFFFFF) ^ (int(step) & 0xFFFFFFFF), seed >> 32], dtype=np.uint64)
+    return philox4x32_10_host(ctr, key)
 
 
 def make_actor(hidden_sizes=(100, 100), activation=None):
