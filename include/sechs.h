@@ -230,6 +230,18 @@ sn_status sn_philox_counter(sn_env* env, int64_t game, uint64_t* counter_host);
                          outputs and exported numpy states; the environment
                          variable SECHS_DEC_WALK overrides the default at
                          sn_create.
+     SN_OPT_DEC_EARLY    1 (default): k_decode touches the next episode's ring
+                         window -- one dword of each 64-byte ring chunk it
+                         spans, five at most -- as soon as the window's
+                         position is known, behind the swap targets, so the
+                         window's own loads at the top of the next episode
+                         find their lines in L2.  The touched bytes are
+                         dropped: they feed nothing and count no overrun, and
+                         the last episode of a dispatch touches nothing.
+                         0: no touches (the form before round 11).  Read at
+                         every k_decode dispatch.  Same records word for
+                         word; the environment variable SECHS_DEC_EARLY
+                         overrides the default at sn_create.
    A pipelined (numpy-compat) rollout records its ordering event on the
    caller's stream before it returns; every later call waits on that event
    (also on the same stream), so the caller may destroy the stream after
@@ -237,7 +249,7 @@ sn_status sn_philox_counter(sn_env* env, int64_t game, uint64_t* counter_host);
 enum { SN_OPT_RING_WORDS = 1, SN_OPT_CHUNK_STEPS = 2, SN_OPT_PIPELINE = 3, SN_OPT_TIMING = 4, SN_OPT_PIPE_GPW = 5,
        SN_OPT_PIPE_LEAD = 6, SN_OPT_PLAY_SPLIT = 7, SN_OPT_PLAY_QUAD = 8, SN_OPT_TWIST_ROUND = 9,
        SN_OPT_TWIST_EVERY = 10, SN_OPT_PIPE_FUSED = 11, SN_OPT_TWIST_SKIP = 12, SN_OPT_PIPE_DEC = 13,
-       SN_OPT_TWIST_DEPTH = 14, SN_OPT_PLAY_GROUP = 15, SN_OPT_DEC_WALK = 16 };
+       SN_OPT_TWIST_DEPTH = 14, SN_OPT_PLAY_GROUP = 15, SN_OPT_DEC_WALK = 16, SN_OPT_DEC_EARLY = 17 };
 sn_status sn_set_option(sn_env* env, int option, int value);
 /* pipelined rollouts whose draws ran past the twisted words (must be 0; a
    nonzero count means those games' draws are wrong) [sync].  The count is

@@ -144,7 +144,12 @@ static __device__ __forceinline__ DecSlow dec_draws_slow(RingPipe rng, uint32_t 
 
 // WALK (SN_OPT_DEC_WALK, the default): the draws too are read by window position (walk_draws); a
 // step the window is too short for goes through the byte buffer as in the other form.
-template <int N, bool WALK>
+//
+// TOUCH (SN_OPT_DEC_EARLY, the default): the next episode's window is touched (RingPipe::touch_at, one dword of each
+// of its ring chunks) as soon as its position is known, right behind the swap targets: a deck's work later the
+// window's own loads find their lines in L2.  The touches' bytes are dropped behind the swaps; they feed nothing, count
+// nothing, and the dispatch's last episode issues none.  The same records either way.
+template <int N, bool WALK, bool TOUCH>
 __global__ __launch_bounds__(kDecBlock) void k_decode(DevState s, DecArgs d) {
     __shared__ __attribute__((aligned(16))) uint8_t lds[kDecBlock * kDecLane];
     const int lane = threadIdx.x & 63;
@@ -199,10 +204,21 @@ __global__ __launch_bounds__(kDecBlock) void k_decode(DevState s, DecArgs d) {
         if constexpr (WALK) rng.take = wt;
         shuffle_targets(rng, buf, jslot, s.C, kDecLane - 1);  // the window's own form (by position), dummy past it
         pos = rng.consumed(buf);
+        const bool more = i + 1 < d.ne;  // wave-uniform
+        uint32_t tv[RingPipe::kPipeTouch] = {};
+        if constexpr (TOUCH) {
+            if (more) RingPipe::touch_at(s, g, pos, tv);
+        }
         pq.mark(PR_TARGETS);
         __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");  // the window reads before the deck's writes
         for (int k = 0; k < s.C; k += 4) *(uint32_t*)(deck + k) = (uint32_t)k * 0x01010101u + 0x03020100u;
         shuffle_apply(deck, jslot, s.C);
+        if constexpr (TOUCH) {
+            if (more) {  // the touches' bytes end here: long back by now (nothing else is in flight: load_at drained)
+#pragma unroll
+                for (int k = 0; k < RingPipe::kPipeTouch; k++) asm volatile("" ::"v"(tv[k]));
+            }
+        }
         pq.mark(PR_APPLY);
         Game<N> G;
         deal_from_deck<N>(deck, s.C, G);

@@ -228,6 +228,8 @@ sn_status sn_create(sn_env** out, int device, int64_t num_games, int num_players
     env_default("SECHS_PLAY_GROUP", 0, 1, e->opt.play_group);
     e->opt.dec_walk = 1;  // k_decode's draws by window position
     env_default("SECHS_DEC_WALK", 0, 1, e->opt.dec_walk);
+    e->opt.dec_early = 1;  // k_decode touches the next window behind the swap targets
+    env_default("SECHS_DEC_EARLY", 0, 1, e->opt.dec_early);
     e->opt.pipe_dec = 1;  // decode-ahead where it applies: 0.0776 -> 0.069 ms per step same box
     env_default("SECHS_PIPE_DEC", 0, 1, e->opt.pipe_dec);
     if (rng_mode == SN_RNG_NUMPY_MT) {
@@ -392,6 +394,10 @@ sn_status sn_set_option(sn_env* e, int option, int value) {
                                // way, so nothing past the pipeline sync every option change begins with (above)
             if (value < 0 || value > 1) return fail(SN_EINVAL, "dec walk must be 0 or 1");
             e->opt.dec_walk = value;
+            return SN_OK;
+        case SN_OPT_DEC_EARLY:  // as SN_OPT_DEC_WALK: the form of k_decode only, read at every dispatch
+            if (value < 0 || value > 1) return fail(SN_EINVAL, "dec early must be 0 or 1");
+            e->opt.dec_early = value;
             return SN_OK;
         case SN_OPT_TWIST_SKIP:
             if (value < 0 || value > 1) return fail(SN_EINVAL, "twist skip must be 0 or 1");
@@ -652,8 +658,12 @@ static sn_status dec_launch(sn_env* e, int64_t e0, int ne, int phi0, int tpar, i
     const dim3 grid((unsigned)((s.B + kDecBlock - 1) / kDecBlock));
     SN_DISPATCH_N(s.N, {
         if constexpr (NN <= kSplitMaxPlayers) {
-            if (e->opt.dec_walk) hipLaunchKernelGGL((k_decode<NN, true>), grid, dim3(kDecBlock), 0, st, s, d);
-            else hipLaunchKernelGGL((k_decode<NN, false>), grid, dim3(kDecBlock), 0, st, s, d);
+            const bool walk = e->opt.dec_walk != 0;
+            const bool touch = e->opt.dec_early != 0;
+            if (walk && touch) hipLaunchKernelGGL((k_decode<NN, true, true>), grid, dim3(kDecBlock), 0, st, s, d);
+            else if (walk) hipLaunchKernelGGL((k_decode<NN, true, false>), grid, dim3(kDecBlock), 0, st, s, d);
+            else if (touch) hipLaunchKernelGGL((k_decode<NN, false, true>), grid, dim3(kDecBlock), 0, st, s, d);
+            else hipLaunchKernelGGL((k_decode<NN, false, false>), grid, dim3(kDecBlock), 0, st, s, d);
         }
     });
     HIP_TRY(hipGetLastError());

@@ -364,6 +364,17 @@ struct RingPipe {
             }
         buf.clear();
     }
+    // one dword of every 64-B ring chunk that the window [c, c + kPipeWin) spans, five at most (a game's 64
+    // consecutive positions are one chunk): the lines are then in L2 when the window's own loads come.  Plain loads
+    // whose bytes are dropped: they count nothing and know no twisted end (a line past it may be under construction
+    // by the concurrent twist; the window's own loads, guarded by `win`, decide what is consumed).
+    static constexpr int kPipeTouch = (63 + kPipeWin - 1) / 64 + 1;
+    static __device__ __forceinline__ void touch_at(const DevState& s, int64_t gg, uint32_t c, uint32_t (&v)[kPipeTouch]) {
+        const uint32_t ch0 = c >> 6, last = ((c & 63u) + (uint32_t)kPipeWin - 1u) >> 6;
+#pragma unroll
+        for (uint32_t k = 0; k < (uint32_t)kPipeTouch; k++)  // past the last chunk: that chunk again (no new line)
+            v[k] = s.pring[ring16(4u * (ch0 + min(k, last)), gg, s.B)].x;
+    }
     __device__ __forceinline__ uint32_t consumed(const ByteBuf& buf) const { return c0 + take - buf.cnt; }
     // forced = the buffer is empty and a draw needs a word now
     __device__ __forceinline__ bool gen(ByteBuf& buf, bool forced) {
@@ -1007,6 +1018,7 @@ struct sn_env {
         int pipe_dec;     // SN_OPT_PIPE_DEC: decode-ahead (k_decode + k_play<RNG_NUMPY_DEC>) where it applies
         int play_group;   // SN_OPT_PLAY_GROUP: decode-ahead plays a call's chunks of one twist group in one k_play launch
         int dec_walk;     // SN_OPT_DEC_WALK: k_decode reads its draws by window position (1) or through the byte buffer (0)
+        int dec_early;    // SN_OPT_DEC_EARLY: k_decode touches the next episode's ring window as soon as its position is known
         int pipe_serial;  // SECHS_PIPE_SERIAL=1 (diagnostics): each twist waits for the play launch before it (no overlap)
         int play_split;   // SN_OPT_PLAY_SPLIT: role-split k_play for lockstep DrunkHamster rollouts
         int twist_every;  // SN_OPT_TWIST_EVERY: a k_mt_ahead beside every K-th play launch (K = 1 .. 5)

@@ -29,6 +29,7 @@ SN_OPT_PIPE_DEC = 13
 SN_OPT_TWIST_DEPTH = 14
 SN_OPT_PLAY_GROUP = 15
 SN_OPT_DEC_WALK = 16
+SN_OPT_DEC_EARLY = 17
 SN_AGENT_RANDOM, SN_AGENT_MCS, SN_AGENT_EXTERNAL = 0, 1, 2
 
 class SnPuct(ctypes.Structure):

@@ -191,6 +191,7 @@ class VecSechsNimmtEnv:
         ("play_split", nat.SN_OPT_PLAY_SPLIT, int), ("twist_every", nat.SN_OPT_TWIST_EVERY, int),
         ("twist_round", nat.SN_OPT_TWIST_ROUND, int), ("twist_depth", nat.SN_OPT_TWIST_DEPTH, int),
         ("play_group", nat.SN_OPT_PLAY_GROUP, int), ("walk_draws", nat.SN_OPT_DEC_WALK, int),
+        ("dec_early", nat.SN_OPT_DEC_EARLY, int),
         ("pipe_dec", nat.SN_OPT_PIPE_DEC, int), ("twist_skip", nat.SN_OPT_TWIST_SKIP, int),
         ("pipeline", nat.SN_OPT_PIPELINE, lambda v: int(bool(v))), ("ring_words", nat.SN_OPT_RING_WORDS, int),
         ("chunk_steps", nat.SN_OPT_CHUNK_STEPS, int),
@@ -198,14 +199,15 @@ class VecSechsNimmtEnv:
 
     def set_option(self, ring_words=None, chunk_steps=None, pipeline=None, pipe_gpw=None, pipe_lead=None,
                    play_split=None, twist_round=None, twist_every=None, twist_skip=None, pipe_dec=None,
-                   twist_depth=None, play_group=None, walk_draws=None):
+                   twist_depth=None, play_group=None, walk_draws=None, dec_early=None):
         """rollout tuning (include/sechs.h SN_OPT_*; all numpy-compat only except play_split,
         the role-split kernel of philox handles; twist_round: whole-round MT twists in
         k_mt_ahead; twist_every: one twist-ahead launch per K = 1 .. 5 play launches; twist_depth:
         0 .. 3 extra rounds a refilling game twists past the lead, chained in LDS; pipe_dec:
         decode-ahead, k_decode + k_play from the records; play_group: decode-ahead plays a call's
         chunks of one twist group in one k_play launch; walk_draws: k_decode reads its draws by
-        window position (1) or through the byte buffer (0)); results never
+        window position (1) or through the byte buffer (0); dec_early: k_decode touches the
+        next episode's ring window as soon as its position is known (1) or not (0)); results never
         depend on it (except the test knobs pipe_lead < 600 and twist_skip = 1, which make
         overruns -- PipeOverrunError -- likely / certain)"""
         given = locals()
