@@ -624,6 +624,34 @@ sn_status sn_per_tree(sn_per* per, double* tree_out, void* stream);
    DDQNAgent: History.sample (replay_buffer.py:233-234) draws
    random.sample(range(len)), the caller draws the slots. */
 sn_status sn_per_gather(sn_per* per, int64_t n, const int32_t* slots, void* rows_out, void* stream);
+/* A clone's replay (the reference's copy_player round-trips the whole agent
+   through torch.save, tournament.py:54-60: the clone is the same buffer).
+   Every slot of dst is overwritten, then its internal nodes are recomputed
+   as after store and update.  src is only read; its pending work must have
+   been enqueued on `stream` as well (the call only enqueues, like every
+   sn_per_* call, and does not wait for another stream).  SN_EINVAL: a NULL
+   argument, dst == src, different row_bytes, different devices.
+     - Equal capacities: a verbatim copy.  Every leaf and row keeps its slot,
+       pointer and num_items are copied (num_items past the capacity too), so
+       dst and src answer the same uniforms with the same tree indices.
+     - Different capacities: the newest rows are re-homed.  held = src's
+       capacity if src has wrapped, else its pointer; src has wrapped exactly
+       when num_items != pointer (before the first wrap both count the stores;
+       after w wraps num_items - pointer = (capacity - 1) * w >= 1).
+       h = min(held, dst's capacity); slot k < h of dst (0 = the
+       oldest) takes the leaf -- src's priority, not the maximum -- and the
+       row of src's slot (pointer - h + k) mod capacity; slots k >= h get a
+       zero leaf and a zero row.  dst's counters become those of h stores
+       into an empty ring: pointer = h mod capacity, num_items = h, less one
+       if h equals the capacity (that store wrapped). */
+sn_status sn_per_inherit(sn_per* dst, const sn_per* src, void* stream);
+/* The verbatim copy from caller-owned device buffers (un-pickling; the
+   export is sn_per_tree's leaves and sn_per_gather of every slot): leaves
+   [capacity] f64, rows [capacity][row_bytes] 16-byte aligned -- NULL exactly
+   when row_bytes is 0 --, neither overlapping dst's own memory; pointer in
+   [0, capacity), num_items >= 0, else SN_EINVAL. */
+sn_status sn_per_import(sn_per* dst, const double* leaves, const void* rows, int64_t pointer, int64_t num_items,
+                        void* stream);
 
 /* ---- Batched DQN family (agents/dqn.py:42-231,304-380,427) ---------------
    Every deciding seat of every game acts together; decisions are addressed

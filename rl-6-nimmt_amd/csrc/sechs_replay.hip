@@ -211,6 +211,33 @@ __global__ void __launch_bounds__(kPerBlock) k_per_write(double* __restrict__ tr
     tree[node] = alpha == 1.0 ? clipped : pow(clipped, alpha);
 }
 
+// sn_per_inherit / sn_per_import: every destination slot is written, so
+// nothing stale survives.  Slot k < h takes the leaf and the payload row of
+// source slot (src_first + k) mod cap_src, slot k >= h a zero leaf and a zero
+// row.  One thread per 16-byte piece of a destination row (one per row
+// without payload), the layout of k_per_store.  src_first < cap_src, h <=
+// min(cap_src, cap_dst); per_rebuild follows.
+__global__ void __launch_bounds__(kPerBlock) k_per_inherit(double* __restrict__ tree, uint8_t* __restrict__ ring,
+                                                           int64_t cap, const double* __restrict__ src_leaves,
+                                                           const uint8_t* __restrict__ src_ring, int64_t cap_src,
+                                                           int64_t src_first, int64_t h, int chunks) {
+    const int per_row = chunks > 0 ? chunks : 1;
+    const int64_t e = (int64_t)blockIdx.x * kPerBlock + threadIdx.x;
+    if (e >= cap * per_row) return;
+    const int64_t k = e / per_row;
+    const int c = (int)(e - k * per_row);
+    double leaf = 0.0;
+    uint4 v = uint4{0u, 0u, 0u, 0u};
+    if (k < h) {
+        int64_t s = src_first + k;
+        if (s >= cap_src) s -= cap_src;
+        leaf = src_leaves[s];
+        if (chunks > 0) v = reinterpret_cast<const uint4*>(src_ring)[s * chunks + c];
+    }
+    if (c == 0) tree[cap - 1 + k] = leaf;
+    if (chunks > 0) reinterpret_cast<uint4*>(ring)[k * chunks + c] = v;
+}
+
 inline unsigned per_grid(int64_t n) { return (unsigned)((n + kPerBlock - 1) / kPerBlock); }
 
 }  // namespace
@@ -250,6 +277,19 @@ void per_rebuild(sn_per* per, hipStream_t st) {
         k_per_rebuild<<<(unsigned)roots, kPerBlock, 0, st>>>(per->tree, per->cap, d0, hi - d0);
         hi = d0;
     }
+}
+
+// all of per's slots from h source slots starting at src_first (k_per_inherit), then the internal nodes
+sn_status per_load(sn_per* per, const double* src_leaves, const uint8_t* src_ring, int64_t cap_src,
+                   int64_t src_first, int64_t h, hipStream_t st) {
+    const int chunks = (int)(per->row_bytes / 16);
+    const int64_t blocks = (per->cap * (chunks > 0 ? chunks : 1) + kPerBlock - 1) / kPerBlock;
+    if (blocks > 0x7FFFFFFF) return set_error(SN_EUNSUPPORTED, "capacity x row pieces exceeds one launch");
+    k_per_inherit<<<(unsigned)blocks, kPerBlock, 0, st>>>(per->tree, per->ring, per->cap, src_leaves, src_ring, cap_src,
+                                                          src_first, h, chunks);
+    per_rebuild(per, st);
+    HIP_TRY(hipGetLastError());
+    return SN_OK;
 }
 
 }  // namespace
@@ -374,6 +414,49 @@ sn_status sn_per_tree(sn_per* per, double* tree_out, void* stream) {
     HIP_TRY(hipSetDevice(per->device));
     HIP_TRY(hipMemcpyAsync(tree_out, per->tree, sizeof(double) * (size_t)(2 * per->cap - 1), hipMemcpyDeviceToDevice,
                            (hipStream_t)stream));
+    return SN_OK;
+}
+
+sn_status sn_per_inherit(sn_per* dst, const sn_per* src, void* stream) {
+    if (!dst || !src) return set_error(SN_EINVAL, "NULL argument");
+    if (dst == src) return set_error(SN_EINVAL, "a replay cannot inherit from itself");
+    if (dst->row_bytes != src->row_bytes) return set_error(SN_EINVAL, "row_bytes of parent and child differ");
+    if (dst->device != src->device) return set_error(SN_EINVAL, "parent and child live on different devices");
+    HIP_TRY(hipSetDevice(dst->device));
+    const double* leaves = src->tree + (src->cap - 1);
+    if (dst->cap == src->cap) {  // verbatim: every slot stays where it is, and so do the counters
+        const sn_status s = per_load(dst, leaves, src->ring, src->cap, 0, src->cap, (hipStream_t)stream);
+        if (s != SN_OK) return s;
+        dst->pointer = src->pointer, dst->num_items = src->num_items;
+        return SN_OK;
+    }
+    // re-home the newest rows, oldest first.  The ring has wrapped exactly when num_items != pointer:
+    // before the first wrap both count the stores, from then on they differ by (capacity - 1) x wraps.
+    const int64_t held = src->num_items != src->pointer ? src->cap : src->pointer;
+    const int64_t h = held < dst->cap ? held : dst->cap;
+    int64_t first = src->pointer - h;
+    if (first < 0) first += src->cap;
+    const sn_status s = per_load(dst, leaves, src->ring, src->cap, first, h, (hipStream_t)stream);
+    if (s != SN_OK) return s;
+    // the counters of h stores into an empty ring (sn_per_store)
+    dst->pointer = h == dst->cap ? 0 : h;
+    dst->num_items = h - (h == dst->cap ? 1 : 0);
+    return SN_OK;
+}
+
+sn_status sn_per_import(sn_per* dst, const double* leaves, const void* rows, int64_t pointer, int64_t num_items,
+                        void* stream) {
+    if (!dst || !leaves) return set_error(SN_EINVAL, "NULL argument");
+    if ((rows == nullptr) != (dst->row_bytes == 0))
+        return set_error(SN_EINVAL, "rows must be NULL exactly for a replay without payload");
+    if (((uintptr_t)rows & 15) != 0) return set_error(SN_EINVAL, "rows must be 16-byte aligned");
+    if (((uintptr_t)leaves & 7) != 0) return set_error(SN_EINVAL, "leaves must be 8-byte aligned");
+    if (pointer < 0 || pointer >= dst->cap) return set_error(SN_EINVAL, "pointer must be in 0..capacity-1");
+    if (num_items < 0) return set_error(SN_EINVAL, "num_items must be >= 0");
+    HIP_TRY(hipSetDevice(dst->device));
+    const sn_status s = per_load(dst, leaves, (const uint8_t*)rows, dst->cap, 0, dst->cap, (hipStream_t)stream);
+    if (s != SN_OK) return s;
+    dst->pointer = pointer, dst->num_items = num_items;
     return SN_OK;
 }
 

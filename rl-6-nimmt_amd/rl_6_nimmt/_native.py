@@ -128,6 +128,8 @@ SIGNATURES = {
     "sn_per_update": ([_P, _I64, _P, _P, ctypes.c_double, ctypes.c_double, ctypes.c_double, _P], _I),
     "sn_per_tree": ([_P, _P, _P], _I),
     "sn_per_gather": ([_P, _I64, _P, _P, _P], _I),
+    "sn_per_inherit": ([_P, _P, _P], _I),
+    "sn_per_import": ([_P, _P, _P, _I64, _I64, _P], _I),
     "sn_dqn_obs": ([_P, _P, _P, _P, _I, _P], _I),
     "sn_dqn_select": ([_P, _P, _P, _I64, ctypes.c_double, _P, _P, _P, _P], _I),
     "sn_dqn_pack": ([_I64, _I64, _P, _P, _P, _P, _P], _I),

@@ -18,7 +18,9 @@ DuellingDDQNAgent ("duelling_ddqn"), DuellingDDQN_PRBAgent
 seat.  So do the noisy variants -- Noisy_DQN ("noisy_dqn"), Noisy_D3QN
 ("noisy_d3qn"), Noisy_D3QN_PRB_NStep ("noisy_d3qn_prb_nstep") -- registered in
 DQN_NOISY_AGENTS: the engine gives every decision its own factorised noise
-(dqn.BatchedDQN.noisy).  Not built: the human UI.
+(dqn.BatchedDQN.noisy).  The *_PRB agents deep-copy and pickle with their
+device replay (replay.DevicePER.clone), so Tournament.copy_player and evolve
+clone a trained one.  Not built: the human UI.
 """
 from .base import Agent
 from .random import DrunkHamster

@@ -37,7 +37,8 @@ Different by construction: exploration draws are Philox, not Python's
 `random` (parity unpinned, like the other engines' samplers), a round
 trains on `updates` x `minibatch` rows, not 10 x 64 per game, and the n-step
 targets and losses are fp32 (the reference's are float64: its n-step reward
-is a Python float).  Not built: replay inheritance for a cloned engine.
+is a Python float).  A clone's engine inherits its parent's replay and
+counters (`inherit`).
 
 A noisy net (utils.nets.NoisyFactorizedLinear layers, plain or duelling:
 `BatchedDQN.noisy`) explores by its noise, and every decision row has its
@@ -624,3 +625,18 @@ class BatchedDQN(BatchedEngine):
     def learn_round(self, optimizer, per_step, updates_per_round):
         """its own schedule: `updates` minibatches per round, every one counted"""
         return len(self.learn(optimizer)) if self.D else None
+
+    def inherit(self, parent):
+        """a clone's engine goes on where its parent's stands, as the
+        reference's copy_player carries the whole agent through its torch.save
+        round trip (tournament.py:54-60): the replay with its priorities and
+        beta (DevicePER.inherit: verbatim at equal capacity, else the newest
+        rows), the episode count behind the epsilon schedule, the update
+        count behind the soft-update cadence, the epsilon log.  Nothing from
+        another kind of engine or another n_steps: those rows carry a
+        different reward field."""
+        if not isinstance(parent, BatchedDQN) or parent.n_steps != self.n_steps:
+            return
+        self.replay.inherit(parent.replay)
+        self.episode, self.update_count = parent.episode, parent.update_count
+        self.eps_history = list(parent.eps_history)

@@ -38,7 +38,8 @@ Agents (the pool of run.py:20-40):
     PyTorch-ROCm, an epsilon-greedy Philox selection; with train=True the
     round's transitions go into the engine's DevicePER ring and the agent
     takes T_STEPS minibatch updates of max(agent.minibatch, slots) rows per
-    round.  A clone's engine starts with an empty replay.
+    round.  A clone's engine inherits its parent's replay, episode and
+    update counts (BatchedDQN.inherit).
 All-DrunkHamster leagues play whole games per launch (sn_league_rollout,
 `fused`); every other league plays sn_reset (seat draw + deal) then 10
 sn_league_step launches per game round.
@@ -54,7 +55,8 @@ builds the engine of a drop-in agent (hyper-parameters, replay size); a round
 is begin_round(dec, agent, train), ten decide(n, record=train), end_round
 (engines with `closes_round`: DQN stores the round's transitions) and
 learn_round -> the optimiser steps to count; inherit(parent) hands a clone's
-engine what its parent's keeps (ACER: the replay).
+engine what its parent's keeps (ACER: the replay; DQN: the replay and its
+counters).
 """
 import copy
 import ctypes
@@ -242,7 +244,7 @@ class BatchedTournament:
 
     def copy_player(self, old_name, new_name, _defer=False):
         """tournament.py:54-60: the clone inherits the tallies, Elo, family and
-        (ACER) replay (the reference round-trips the module through
+        (ACER, DQN) replay (the reference round-trips the module through
         temp_model.pt); it plays from the next game on"""
         if self.mode == "fused" and not _defer:
             raise NotImplementedError("the fused all-DrunkHamster league has drawn its next seats already; change the "

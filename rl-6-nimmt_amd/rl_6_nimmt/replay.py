@@ -19,6 +19,15 @@ stream of the device; nothing synchronises.
 
 There is no CPU fallback: the handle is created on first use and that needs
 the GPU.  Constructing a `DevicePER` touches nothing.
+
+Clones: `inherit(parent)` takes the parent's leaves, rows and
+hyper-parameters on the device (sn_per_inherit) -- verbatim at equal
+capacity, else the newest rows re-homed, oldest first; `inherit_host` is the
+torch model of that rule and the kernel is held to it.  `copy.deepcopy` is
+`clone()`, an equal-capacity `inherit`.  Pickling (`torch.save` of an agent)
+exports the leaves and the ring to CPU tensors, which synchronises; loading
+keeps them on the host until the handle is next created (sn_per_import), so
+unpickling touches no GPU either.
 """
 import ctypes
 
@@ -26,6 +35,36 @@ import numpy as np
 import torch
 
 from . import _native as nat
+
+
+_HYPER = ("absolute_error_upper", "epsilon", "alpha", "beta", "beta_increment")
+
+
+def inherit_host(leaves, rows, pointer, num_items, capacity):
+    """sn_per_inherit in torch: what a replay of `capacity` slots takes from a
+    parent with `leaves` f64 [cap], `rows` [cap, row_bytes] (or None) and the
+    counters `pointer`, `num_items` -> (leaves', rows', pointer', num_items').
+    Equal capacities: everything as it is.  Else the newest h = min(held,
+    capacity) slots, oldest first, into slots 0 .. h-1 with the parent's
+    priorities, zeros behind them, and the counters of h stores into an empty
+    ring; held = cap once the parent has wrapped (num_items != pointer), its
+    pointer before."""
+    leaves = torch.as_tensor(leaves, dtype=torch.float64).reshape(-1)
+    cap_src, cap, pointer, num_items = int(leaves.numel()), int(capacity), int(pointer), int(num_items)
+    if rows is not None:
+        rows = torch.as_tensor(rows).reshape(cap_src, -1)
+    if cap == cap_src:
+        return leaves.clone(), None if rows is None else rows.clone(), pointer, num_items
+    held = cap_src if num_items != pointer else pointer
+    h = min(held, cap)
+    src = (pointer - h + torch.arange(h, device=leaves.device)) % cap_src
+    new_leaves = torch.zeros(cap, dtype=torch.float64, device=leaves.device)
+    new_leaves[:h] = leaves[src]
+    new_rows = None
+    if rows is not None:
+        new_rows = torch.zeros((cap, rows.shape[1]), dtype=rows.dtype, device=rows.device)
+        new_rows[:h] = rows[src.to(rows.device)]
+    return new_leaves, new_rows, h % cap, h - (1 if h == cap else 0)
 
 
 class DevicePER:
@@ -39,6 +78,7 @@ class DevicePER:
         self._device_arg = device
         self.device = None
         self._h = None
+        self._saved = None  # (leaves, ring or None, pointer, num_items) on the host, loaded when the handle is created
         # replay_buffer.py:143-148
         self.absolute_error_upper = 1.0
         self.epsilon = 0.01
@@ -59,6 +99,13 @@ class DevicePER:
             with torch.cuda.device(self.device):
                 nat.check(nat.lib().sn_per_create(ctypes.byref(h), self.capacity, self.row_bytes, idx), "sn_per_create")
             self._h = h
+            if self._saved is not None:  # an unpickled state (or a clone of one)
+                leaves, ring, pointer, num_items = self._saved
+                leaves = leaves.to(self.device, torch.float64).contiguous()
+                ring = None if ring is None else ring.to(self.device).contiguous()
+                nat.check(nat.lib().sn_per_import(h, nat.ptr(leaves), nat.ptr(ring), pointer, num_items,
+                                                  self._stream()), "sn_per_import")
+                self._saved = None
         return self._h
 
     def close(self):
@@ -72,12 +119,75 @@ class DevicePER:
         except Exception:
             pass
 
+    # ------------------------------------------------------------ clones
+    def inherit(self, parent):
+        """take over `parent`'s replay and hyper-parameters; whatever this
+        one held is gone.  Equal capacities: verbatim, slot for slot, with
+        the parent's counters.  Else the parent's newest rows, oldest first,
+        up to this capacity, at the parent's priorities (inherit_host; DESIGN
+        §4c).  Enqueued on the current stream, where the parent's own calls
+        went.  A parent nothing was ever stored into leaves this one empty
+        and touches no GPU."""
+        if parent is self:
+            raise ValueError("a replay cannot inherit from itself")
+        if parent.row_bytes != self.row_bytes:
+            raise ValueError(f"the parent's rows hold {parent.row_bytes} bytes, not {self.row_bytes}")
+        for k in _HYPER:
+            setattr(self, k, getattr(parent, k))
+        if parent._h is None:  # nothing on the device: empty, or a loaded state still on the host
+            self.close()
+            self._saved = None
+            if parent._saved is not None:
+                self._saved = inherit_host(*parent._saved, self.capacity)
+            return
+        self._saved = None  # loaded state this one never used: overwritten like the rest
+        h = self._handle()
+        nat.check(nat.lib().sn_per_inherit(h, parent._h, self._stream()), "sn_per_inherit")
+
+    def clone(self):
+        """a new DevicePER of the same capacity, row_bytes and device holding
+        the same replay: same uniforms, same samples; from there on the two
+        are independent.  Of one without a handle: another without a handle."""
+        new = DevicePER(self.capacity, self.row_bytes, device=self._device_arg if self.device is None else self.device)
+        new.inherit(self)
+        return new
+
+    def __deepcopy__(self, memo):
+        memo[id(self)] = new = self.clone()
+        return new
+
+    def __getstate__(self):
+        """constructor arguments, hyper-parameters, counters and -- when a
+        handle exists -- the leaves (f64) and the ring (uint8) as CPU tensors:
+        this waits for the device"""
+        state = {"capacity": self.capacity, "row_bytes": self.row_bytes, "device": self._device_arg,
+                 **{k: getattr(self, k) for k in _HYPER}}
+        if self._h is not None:
+            _, pointer, num_items = self._counters()
+            leaves = self.tree()[self.capacity - 1:].cpu()
+            ring = None
+            if self.row_bytes:
+                ring = self.gather(torch.arange(self.capacity, dtype=torch.int32, device=self.device)).cpu()
+            state["saved"] = (leaves, ring, pointer, num_items)
+        elif self._saved is not None:
+            state["saved"] = self._saved
+        return state
+
+    def __setstate__(self, state):
+        """touches no GPU: the arrays stay on the host until the handle is
+        next created; `len` and `pointer` answer from the kept counters"""
+        self.capacity, self.row_bytes, self._device_arg = state["capacity"], state["row_bytes"], state["device"]
+        self.device, self._h = None, None
+        self._saved = state.get("saved")
+        for k in _HYPER:
+            setattr(self, k, state[k])
+
     def _stream(self):
         return nat.stream_handle(self.device)
 
     def _counters(self):
         if self._h is None:
-            return self.capacity, 0, 0
+            return (self.capacity, 0, 0) if self._saved is None else (self.capacity,) + tuple(self._saved[2:])
         c, p, n = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
         nat.check(nat.lib().sn_per_info(self._h, ctypes.byref(c), ctypes.byref(p), ctypes.byref(n)), "sn_per_info")
         return c.value, p.value, n.value

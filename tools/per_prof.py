@@ -7,14 +7,16 @@ and the torch leg of an operation alternate; medians over `--reps`.
   big    capacity 2^20, 112-byte rows (two int8 observations, action, reward,
          done), store / sample / update of 65 536 -- the batched learner's shape;
   small  capacity 100 000, no rows, n = 64 -- the drop-in agents' shape: a
-         launch-overhead figure, not a bandwidth one.
+         launch-overhead figure, not a bandwidth one;
+  inherit  a clone's replay (DevicePER.inherit) at the big shape,
+         into the same and into half the capacity: see run_inherit.
 The torch yardstick (TorchPER) keeps flat leaves and the ring: store = max +
 scatter + index_copy_; sample = cumsum + searchsorted + index_select (+ the
 weights); update = clamp + pow + scatter.  For time only: a cumsum orders the
 additions differently from the tree, and its scatter of a repeated index is
 not ordered.  Algorithmic bytes: algorithmic_bytes() below.
 
-Usage:  python tools/per_prof.py [--reps 30] [--warmup 5] [--only big|small]
+Usage:  python tools/per_prof.py [--reps 30] [--warmup 5] [--only big|small|inherit]
         [--native-only] [--out per_prof.json]
 (--native-only: the native legs alone, for a kernel trace of its own:
  rocprofv3 --kernel-trace --stats -d <dir> -- python tools/per_prof.py --native-only --reps 5)
@@ -144,6 +146,59 @@ def run_shape(name, reps, warmup, native_only):
     return out
 
 
+def run_inherit(reps, warmup, native_only):
+    """DevicePER.inherit (one k_per_inherit launch + the rebuild) at the big shape, into a child of the same
+    capacity (verbatim) and of half of it (the newest half re-homed), against the same result put together
+    from PyTorch ops: the parent's leaves (tree() slice) and rows (gather(arange)), an index_select into the
+    child's order, sn_per_import.  Once per clone, not per step: a correctness path, timed for the record."""
+    from rl_6_nimmt import _native as nat
+    from rl_6_nimmt.replay import DevicePER
+
+    cap, rb, n = SHAPES["big"]
+    dev = torch.device("cuda", torch.cuda.current_device())
+    g = torch.Generator(device=dev)
+    g.manual_seed(1)
+    parent = DevicePER(cap, row_bytes=rb, device=dev)
+    for at in range(0, cap + n, n):  # wrapped, the pointer at n
+        parent.store(torch.randint(0, 256, (n, rb), dtype=torch.uint8, device=dev, generator=g))
+    parent.update(torch.arange(cap - 1, 2 * cap - 1, device=dev), torch.rand(cap, dtype=torch.float64, device=dev, generator=g))
+    every = torch.arange(cap, dtype=torch.int32, device=dev)
+    out = {"capacity": cap, "row_bytes": rb, "reps": reps}
+    for name, c in (("equal", cap), ("halved", cap // 2)):
+        h = min(cap, c)
+        child, built = DevicePER(c, row_bytes=rb, device=dev), DevicePER(c, row_bytes=rb, device=dev)
+        src = torch.arange(cap, device=dev) if c == cap else (parent.pointer - h + torch.arange(h, device=dev)) % cap
+        counters = (parent.pointer, len(parent)) if c == cap else (h % c, h - (h == c))
+
+        def native():
+            child.inherit(parent)
+
+        def yard():
+            leaves = parent.tree()[cap - 1:].index_select(0, src)
+            rows = parent.gather(every).index_select(0, src)
+            nat.check(nat.lib().sn_per_import(built._handle(), nat.ptr(leaves), nat.ptr(rows), *counters,
+                                              built._stream()), "sn_per_import")
+
+        t_n, t_y = [], []
+        for r in range(warmup + reps):
+            a = timed(native)
+            b = None if native_only else timed(yard)
+            if r >= warmup:
+                t_n.append(a)
+                t_y.append(b)
+        nbytes = h * (8 + rb) + c * (8 + rb) + 16 * c  # kept slots read, every child slot written, the rebuild
+        res = {"child_capacity": c, "bytes": nbytes, "native_us": statistics.median(t_n), "native_min_us": min(t_n),
+               "native_max_us": max(t_n)}
+        res["native_GBps"] = nbytes / res["native_us"] / 1e3
+        if not native_only:
+            assert torch.equal(child.tree(), built.tree()) and torch.equal(child.gather(every[:c]), built.gather(every[:c]))
+            assert (child.pointer, len(child)) == (built.pointer, len(built))
+            res.update(torch_us=statistics.median(t_y), torch_min_us=min(t_y), torch_max_us=max(t_y))
+            res["torch_over_native"] = res["torch_us"] / res["native_us"]
+        out[name] = res
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=30)
@@ -156,6 +211,8 @@ def main():
         sys.exit("per_prof: no GPU -- times are taken on the device or not at all")
     result = {name: run_shape(name, args.reps, args.warmup, args.native_only)
               for name in SHAPES if not args.only or name == args.only}
+    if not args.only or args.only == "inherit":
+        result["inherit"] = run_inherit(args.reps, args.warmup, args.native_only)
     text = json.dumps(result, indent=1)
     print(text)
     if args.out:
