@@ -133,6 +133,47 @@ sn_status sn_mt_set(sn_env* env, int64_t game, const uint32_t* key_host, int32_t
 /* philox word counter of game g [sync] */
 sn_status sn_philox_counter(sn_env* env, int64_t game, uint64_t* counter_host);
 
+/* ---- Whole-handle snapshots (checkpoint / resume, resharding) -------------
+   A snapshot is one contiguous blob in DEVICE memory, 16-byte aligned: a
+   fixed header (magic, format version, record size; B, N, C, rng_mode, seed,
+   game_offset; the league configuration; the host fields phase / lg_phase),
+   then one fixed-size record per game, game-major: game g at header_bytes +
+   g * record_bytes.  A record holds the game (hands, rows, scores, episode
+   sums and count), on tournament handles the seat word and the MCS card
+   memory, and the RNG in canonical form: numpy-MT as np.random.get_state()'s
+   (pos, key[624]) at the play consumer's position, Philox as its 64-bit word
+   counter.  Records do not depend on the SN_OPT_* settings or on where the
+   pipelines stand, so a range of records is the state of a shard
+   (csrc/sechs_snapshot.h owns the layout; DESIGN.md has the table of what is
+   saved and what the next launch rebuilds).
+   sn_state_bytes: header + num_games records, pure host arithmetic (no GPU
+   is touched); league != 0: the records of a tournament handle.  -1 for
+   arguments out of range.  sn_state_size: the same for a handle as it is
+   configured now.
+   sn_state_save: behind the pipeline sync, on `stream`; the handle is only
+   read (it plays on exactly as without the save).  SN_EINVAL: NULL, a blob
+   not 16-byte aligned or smaller than sn_state_size; SN_ERNG: the host
+   mirror shows that the handle has counted a pipeline overrun (its streams
+   are lost).  The mirror lags the device, and the call does not wait for
+   it: the kernel writes the device's count, as it stands behind the
+   pipeline sync, into the header, and sn_state_load refuses (SN_EINVAL) a
+   blob whose count is not zero.
+   sn_state_load [sync]: game g of the handle takes record first + g.  The
+   header is read back to the host and checked before anything is launched
+   or any handle state changes: magic, version, record size, N, C, rng_mode
+   and seed must equal the handle's, the league configuration
+   (sn_league_config and sn_league_agents) too, first + B must not pass the
+   blob's records, blob_bytes must cover them, and blob.game_offset + first
+   must equal the handle's game_offset -- every Philox stream and every
+   engine draw is keyed by the global game id.  A mismatch is SN_EINVAL with
+   a message and the handle is untouched.  After a load the overrun count is
+   zero and the next rollout starts its pipeline from the plain state. */
+int64_t sn_state_bytes(int64_t num_games, int num_players, int rng_mode, int league, int64_t* header_bytes,
+                       int64_t* record_bytes);
+int64_t sn_state_size(const sn_env* env);
+sn_status sn_state_save(sn_env* env, void* blob, int64_t blob_bytes, void* stream);
+sn_status sn_state_load(sn_env* env, const void* blob, int64_t blob_bytes, int64_t first, void* stream);
+
 /* Tuning knobs of the numpy-compat DrunkHamster rollout (results never
    depend on them; the tests run both ways):
      SN_OPT_RING_WORDS   words each game's stream is twisted ahead per

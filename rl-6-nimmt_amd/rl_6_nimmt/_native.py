@@ -86,6 +86,10 @@ SIGNATURES = {
     "sn_mt_get": ([_P, _I64, _P, _P], _I),
     "sn_mt_set": ([_P, _I64, _P, ctypes.c_int32], _I),
     "sn_philox_counter": ([_P, _I64, _P], _I),
+    "sn_state_bytes": ([_I64, _I, _I, _I, _P, _P], _I64),
+    "sn_state_size": ([_P], _I64),
+    "sn_state_save": ([_P, _P, _I64, _P], _I),
+    "sn_state_load": ([_P, _P, _I64, _I64, _P], _I),
     "sn_set_option": ([_P, _I, _I], _I),
     "sn_pipe_errors": ([_P, _P], _I),
     "sn_kernel_times": ([_P, _P, _P, _P], _I),

@@ -427,3 +427,25 @@ class BatchedACER(BatchedEngine):
                     dst[b].copy_(src[a])
                 self.rep_nd[b] = parent.rep_nd[a]
         self.episodes = n
+
+    _REPLAY = ("rep_rows", "rep_act", "rep_logp", "rep_rew")
+
+    def state_dict(self):
+        """the base counters, the replay ring verbatim (CPU tensors), its counters and the state of the
+        generator the off-policy picks draw from"""
+        sd = super().state_dict()
+        sd.update({k: getattr(self, k).cpu() for k in self._REPLAY})
+        sd.update(episodes=self.episodes, rep_nd=list(self.rep_nd), gen_state=self._gen.get_state().cpu())
+        return sd
+
+    def load_state_dict(self, sd):
+        super().load_state_dict(sd)
+        for k in self._REPLAY:
+            if getattr(self, k).shape != sd[k].shape:
+                raise ValueError(f"BatchedACER.load_state_dict: {k} is {tuple(sd[k].shape)} in the checkpoint, "
+                                 f"{tuple(getattr(self, k).shape)} here (another capacity or slot count)")
+        with torch.no_grad():
+            for k in self._REPLAY:
+                getattr(self, k).copy_(sd[k])
+        self.episodes, self.rep_nd = int(sd["episodes"]), list(sd["rep_nd"])
+        self._gen.set_state(sd["gen_state"].cpu())

@@ -20,7 +20,11 @@ seat.  So do the noisy variants -- Noisy_DQN ("noisy_dqn"), Noisy_D3QN
 DQN_NOISY_AGENTS: the engine gives every decision its own factorised noise
 (dqn.BatchedDQN.noisy).  The *_PRB agents deep-copy and pickle with their
 device replay (replay.DevicePER.clone), so Tournament.copy_player and evolve
-clone a trained one.  Not built: the human UI.
+clone a trained one.  A whole league of these agents is checkpointed with
+league.BatchedTournament.save / load (the agents through torch.save, their
+engines through engine.BatchedEngine.state_dict / load_state_dict, the
+handle through VecSechsNimmtEnv.state_dict / load_state_dict).  Not built:
+the human UI.
 """
 from .base import Agent
 from .random import DrunkHamster

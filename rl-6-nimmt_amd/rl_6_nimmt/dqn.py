@@ -640,3 +640,23 @@ class BatchedDQN(BatchedEngine):
         self.replay.inherit(parent.replay)
         self.episode, self.update_count = parent.episode, parent.update_count
         self.eps_history = list(parent.eps_history)
+
+    def state_dict(self):
+        """the base counters, the replay through DevicePER's own export (its pickle form: leaves, ring,
+        pointer, num_items, hyper-parameters with beta -- no second format), the episode count behind the
+        epsilon schedule, the update count behind the soft-update cadence and the epsilon log"""
+        sd = super().state_dict()
+        sd.update(replay=self.replay.__getstate__(), episode=self.episode, update_count=self.update_count,
+                  eps_history=list(self.eps_history))
+        return sd
+
+    def load_state_dict(self, sd):
+        super().load_state_dict(sd)
+        rep = sd["replay"]
+        if rep["capacity"] != self.replay.capacity or rep["row_bytes"] != self.replay.row_bytes:
+            raise ValueError(f"BatchedDQN.load_state_dict: the checkpoint's replay holds {rep['capacity']} rows of "
+                             f"{rep['row_bytes']} bytes, this engine's {self.replay.capacity} of {self.replay.row_bytes}")
+        self.replay.close()  # whatever it held is gone; the saved arrays load when the handle is next created
+        self.replay.__setstate__(dict(rep, device=self.env.device))
+        self.episode, self.update_count = int(sd["episode"]), int(sd["update_count"])
+        self.eps_history = list(sd["eps_history"])

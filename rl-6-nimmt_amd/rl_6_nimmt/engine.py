@@ -342,6 +342,17 @@ class BatchedEngine:
     def inherit(self, parent):
         """a clone's engine takes over what its parent's engine keeps across rounds (nothing here)"""
 
+    def state_dict(self):
+        """what the engine keeps across rounds, on the CPU (checkpoints: BatchedTournament.save): the decision
+        counter every Philox draw is keyed by, and the rows counter.  The net and its optimiser are the
+        agent's; the device copy of the net, the decision list and the recorded decisions are rebuilt by the
+        next round."""
+        return {"step_id": self.step_id, "rows_evaluated": self.rows_evaluated}
+
+    def load_state_dict(self, sd):
+        """restore `state_dict()` into an engine built as usual (from_agent) over the restored handle"""
+        self.step_id, self.rows_evaluated = int(sd["step_id"]), int(sd["rows_evaluated"])
+
 
 def decision_forwards(actor, decisions, d0, d1, dev):
     """the training forward of every recorded decision batch's root rows in ONE

@@ -57,6 +57,13 @@ is begin_round(dec, agent, train), ten decide(n, record=train), end_round
 learn_round -> the optimiser steps to count; inherit(parent) hands a clone's
 engine what its parent's keeps (ACER: the replay; DQN: the replay and its
 counters).
+
+Checkpoints: BatchedTournament.save(path) / BatchedTournament.load(path,
+device=None) (state_dict / load_state_dict underneath) write and rebuild
+the whole league between two play_games calls -- the handle through
+VecSechsNimmtEnv.state_dict (a device snapshot, sn_state_save), every engine
+through its state_dict / load_state_dict; the resumed league plays what the
+uninterrupted one would.
 """
 import copy
 import ctypes
@@ -721,6 +728,97 @@ class BatchedTournament:
         if self.env is not None:
             self.env.close()
             self.env = None
+
+    # ------------------------------------------------------------ checkpoint / resume
+    _ARGS = ("num_slots", "min_players", "max_players", "seed", "game_offset", "rng", "elo_initial", "elo_k",
+             "net_dtype", "train", "fused", "distributed", "baseline_num_games", "baseline_condition",
+             "updates_per_round")
+
+    def state_dict(self):
+        """The whole league between two play_games calls, on the host (run.py:45 pickles its Tournament):
+        the constructor arguments; the roster in order with active / descendants / kinds; the agents (with
+        their optimisers) and the baseline agents through one torch.save of our own objects, as copy_player
+        falls back to; the tallies, Elo, position and baseline lists; the records (CPU) with their rosters
+        and the fold mark; the counters; the handle's device snapshot (VecSechsNimmtEnv.state_dict); every
+        engine's state (engine.BatchedEngine.state_dict); torch's CPU and device generator states (DQN's
+        randperm and the noisy minibatch forwards draw from them).  A roster change not yet configured
+        (copy_player / remove_player since the last game) is configured first, as the next play_games would,
+        so that a clone's engine has inherited before it is saved.  distributed=True: every rank saves its own
+        shard (its slots, its records); the restored ranks must form the same world."""
+        if self.env is not None and self._dirty:
+            self._configure()
+        dev = None if self.env is None else self.env.device
+        buf = io.BytesIO()
+        torch.save({"agents": self.agents, "baseline_agents": self.baseline_agents}, buf)
+        return {
+            "format": 1,
+            "args": {k: getattr(self, k) for k in self._ARGS},
+            "device": None if self.device is None else str(self.device),
+            "names": list(self.names), "active": dict(self.active), "descendants": dict(self.descendants),
+            "kinds": dict(self.kinds), "objects": buf.getvalue(),
+            "stats": self.stats.copy(), "elos": self.elos.copy(),
+            "positions": {n: [np.array(p) for p in v] for n, v in self.positions.items()},
+            "baseline_scores": {n: list(v) for n, v in self.baseline_scores.items()},
+            "baseline_positions": {n: list(v) for n, v in self.baseline_positions.items()},
+            "baseline_wins": {n: list(v) for n, v in self.baseline_wins.items()},
+            "_baseline_calls": self._baseline_calls,
+            "records": [(r.cpu(), ids.clone()) for r, ids in self.records],
+            "record_names": [tuple(t) for t in self.record_names], "_seen": self._seen,
+            "total_games": self.total_games, "optimizer_steps": dict(self.optimizer_steps),
+            "q6_slot_rounds": self.q6_slot_rounds, "mode": self.mode,
+            "env": None if self.env is None else self.env.state_dict(),
+            "engines": {n: e.state_dict() for n, e in self.engines.items()},
+            "torch_rng": torch.get_rng_state(),
+            "device_rng": None if dev is None else torch.cuda.get_rng_state(dev),
+        }
+
+    def load_state_dict(self, sd, device=None):
+        """become the league `state_dict()` saved: whatever this object held is dropped, the handle is rebuilt
+        (_start / _configure as usual, then the snapshot is loaded into it), the engines are created as usual
+        (from_agent) and then loaded -- not inherited.  device: where to rebuild it (default: where it was)."""
+        if sd.get("format") != 1:
+            raise ValueError("not a BatchedTournament checkpoint of this format")
+        self.close()
+        self.engines, self._inherit, self._dirty = {}, {}, False
+        for k, v in sd["args"].items():
+            setattr(self, k, v)
+        self.device = device if device is not None else sd["device"]
+        objs = torch.load(io.BytesIO(sd["objects"]), weights_only=False,  # our own objects, as in copy_player
+                          map_location=None if device is None else torch.device(device))
+        self.agents, self.baseline_agents = objs["agents"], objs["baseline_agents"]
+        self.names, self.active = list(sd["names"]), dict(sd["active"])
+        self.descendants, self.kinds = dict(sd["descendants"]), dict(sd["kinds"])
+        self.stats, self.elos = sd["stats"].copy(), sd["elos"].copy()
+        self.positions = {n: [np.array(p) for p in v] for n, v in sd["positions"].items()}
+        for k in ("baseline_scores", "baseline_positions", "baseline_wins"):
+            setattr(self, k, {n: list(v) for n, v in sd[k].items()})
+        self._baseline_calls = sd["_baseline_calls"]
+        self.record_names, self._seen = [tuple(t) for t in sd["record_names"]], sd["_seen"]
+        self.total_games, self.optimizer_steps = sd["total_games"], dict(sd["optimizer_steps"])
+        self.q6_slot_rounds, self.mode = sd["q6_slot_rounds"], None
+        self.records = [(r, ids) for r, ids in sd["records"]]
+        if sd["env"] is not None:
+            self._start()
+            if self.mode != sd["mode"]:
+                raise ValueError(f"the checkpoint's league played in {sd['mode']!r} mode, its roster gives {self.mode!r}")
+            self.env.load_state_dict(sd["env"])
+            for n, e in sd["engines"].items():
+                self.engines[n].load_state_dict(e)
+            self.records = [(r.to(self.env.device), ids) for r, ids in self.records]
+            if sd["device_rng"] is not None:
+                torch.cuda.set_rng_state(sd["device_rng"], self.env.device)
+        torch.set_rng_state(sd["torch_rng"])
+        return self
+
+    def save(self, path):
+        """torch.save of state_dict() to `path` (distributed=True: every rank its own file)"""
+        torch.save(self.state_dict(), path)
+
+    @classmethod
+    def load(cls, path, device=None):
+        """the league `save(path)` wrote, rebuilt on `device` (default: where it was), ready for play_games"""
+        sd = torch.load(path, map_location="cpu", weights_only=False)  # written by save() above
+        return cls(sd["args"]["num_slots"]).load_state_dict(sd, device=device)
 
 
 def league_agent_stats(records, num_agents, max_players):

@@ -247,6 +247,37 @@ class VecSechsNimmtEnv:
         torch.cuda.current_stream(self.device).synchronize()
         nat.check(nat.lib().sn_mt_set(self._h, game, key.ctypes.data_as(ctypes.c_void_p), int(pos)), "sn_mt_set")
 
+    # ------------------------------------------------------------ checkpoint / resume
+    def snapshot(self):
+        """the whole handle as one uint8 device tensor (sn_state_save on the current stream; the format is
+        csrc/sechs_snapshot.h's, rl_6_nimmt/snapshot.py reads it on the host).  The handle is only read."""
+        n = nat.lib().sn_state_size(self._h)
+        if n < 0:
+            nat.check(nat.SN_EINVAL, "sn_state_size")
+        blob = self._empty((n,), torch.uint8)
+        nat.check(nat.lib().sn_state_save(self._h, nat.ptr(blob), n, self._stream()), "sn_state_save")
+        return blob
+
+    def load_snapshot(self, blob, first=0):
+        """game g takes record first + g of `blob` (a uint8 tensor; moved to the device if needed) [sync].
+        Raises ValueError, leaving the handle untouched, unless the blob fits it (include/sechs.h)."""
+        blob = torch.as_tensor(blob, dtype=torch.uint8).to(self.device).contiguous()
+        nat.check(nat.lib().sn_state_load(self._h, nat.ptr(blob), blob.numel(), int(first), self._stream()),
+                  "sn_state_load")
+
+    def state_dict(self):
+        """{"blob": the snapshot as a uint8 CPU tensor, and the constructor arguments} -- everything a later
+        `VecSechsNimmtEnv(**args)` + `load_state_dict` needs to play on exactly where this handle stands
+        (a tournament handle is configured first: BatchedTournament.load does)"""
+        return {"blob": self.snapshot().cpu(), "num_games": self.num_games, "num_players": self.num_players,
+                "num_cards": self.num_cards, "seed": self.seed, "game_offset": self.game_offset, "rng": self.rng,
+                "include_summaries": self.include_summaries}
+
+    def load_state_dict(self, sd, first=0):
+        """restore `state_dict()`'s snapshot: this handle's game g takes the saved game first + g, so a handle
+        of fewer games at game_offset = saved game_offset + first takes a shard of it"""
+        self.load_snapshot(sd["blob"], first)
+
     def philox_counter(self, game=0):
         c = ctypes.c_uint64()
         torch.cuda.current_stream(self.device).synchronize()
