@@ -385,8 +385,13 @@ sn_status sn_league_seats(sn_env* env, uint32_t* out, void* stream);
    SN_AGENT_RANDOM after sn_league_config):
      SN_AGENT_RANDOM    DrunkHamster, drawn in-kernel from the slot's stream
      SN_AGENT_MCS       MCSAgent(mc_per_card[a], mc_max[a]) (agents/mcts.py:17-188):
-                        card memory and the reference-exact search on the
-                        slot's numpy stream (numpy handles only)
+                        the card memory and the search.  numpy handles: the
+                        reference-exact search on the slot's stream.  Philox
+                        handles: one stream per playout, by the stream law at
+                        sn_league_step -- the reference's search in law, not
+                        draw for draw; mc_max[a] > 1 << 20 is SN_EINVAL
+                        there (a playout's number is a 20-bit field of its
+                        stream word)
      SN_AGENT_EXTERNAL  the caller plays the seat (the net agents: their
                         batched engines pick the card, sn_puct over the
                         handle's decision list, sn_puct.dec_list)
@@ -396,10 +401,11 @@ sn_status sn_league_seats(sn_env* env, uint32_t* out, void* stream);
 enum { SN_AGENT_RANDOM = 0, SN_AGENT_MCS = 1, SN_AGENT_EXTERNAL = 2 };
 sn_status sn_league_agents(sn_env* env, const int32_t* kinds_host, const int32_t* mc_per_card_host,
                            const int32_t* mc_max_host);
-/* One env-step of every slot's current game (numpy handles; sn_reset then
-   10 steps per game): seats in seat order as GameSession calls
-   them (play.py:38-41) -- RANDOM and MCS seats draw from the slot's stream in
-   the reference's exact order, EXTERNAL seats play actions [B][N] (checked
+/* One env-step of every slot's current game (sn_reset then 10 steps per
+   game): seats in seat order as GameSession calls
+   them (play.py:38-41) -- on a numpy handle RANDOM and MCS seats draw from
+   the slot's stream in the reference's exact order, on a Philox handle by
+   the stream law below; EXTERNAL seats play actions [B][N] (checked
    against the hand, env.py:114-118).  A game that ends (every 10th step)
    writes records [B][1 + N] (seats word, GameSession.results[0]); the
    slots' next games start with sn_reset (seat draw, then deal:
@@ -411,7 +417,37 @@ sn_status sn_league_agents(sn_env* env, const int32_t* kinds_host, const int32_t
    memory has moved on -- the slot no longer follows the reference's stream
    and the caller must treat it as failed; the batched tournament raises right
    after such a step), status [B] |= 1 where an MCSAgent move got no playout
-   (the reference raises IndexError there, quirk Q6). */
+   (the reference raises IndexError there, quirk Q6).
+
+   The stream law of a Philox tournament handle (rng_mode SN_RNG_PHILOX,
+   seed = seed_hi << 32 | seed_lo; slot g, gid = game_offset + g).
+   Main stream: key (seed_lo, seed_hi), stream gid, word counter ctr[g]
+   (sn_philox_counter).  sn_reset draws the seats, then the deal.  In
+   sn_league_step the RANDOM seats draw legal[random_interval(n - 1)] from
+   it in seat order; EXTERNAL and MCS seats draw nothing from it.  (An
+   illegal external card leaves the slot's counter where it was.)
+   MCS decision of seat p at a hand of n >= 2 cards in a game of k players,
+   c0 = ctr[g] as the step begins, before any RANDOM seat of the step draws:
+   playout j, 0 <= j < n_mc = min(mc_max, mc_per_card * n!), draws from a
+   Philox stream of its own, from word 0:
+     key     (seed_lo ^ lo32(c0), seed_hi ^ hi32(c0) ^ 0x4D435331)
+     stream  (uint32)gid << 32 | p << 28 | j << 8 | n
+   (the layout of the net engines' decision streams: j where a rollout number
+   sits, n in the low byte).  Within a game n differs from step to step, and
+   between two games sn_reset draws at least the deal, so (c0, n) never
+   repeats for a (gid, p).  None of this is state: a snapshot taken
+   mid-round resumes the same searches.
+   A playout draws in the order of the reference's loop body (mcts.py:108-154
+   with uniform moves): from the ascending card memory of A cards, numpy's
+   shuffle (i = A-1 .. 1: j = random_interval(i), swap); opponent q = 1 ..
+   k-1 holds sorted(cards[(q-1) n : q n]); for t < n and seat q = 0 .. k-1
+   idx = random_interval(n - t - 1), seat 0's first idx is the move the
+   playout is filed under; outcome = -(seat 0's penalties).
+   The move is _choose_action_from_outcomes': the best mean in legal order,
+   strict '>', over integer sums and counts (so it does not depend on which
+   lane ran which playout); a legal move without a playout sets status bit 1
+   and the best sampled move is played (quirk Q6).  A one-card hand is
+   played without a search. */
 sn_status sn_league_step(sn_env* env, const int32_t* actions, int32_t* rewards, int32_t* played, int32_t* records,
                          int32_t* invalid, int32_t* status, void* stream);
 /* Sequential multiplayer Elo over game records in the given order (host
@@ -478,6 +514,21 @@ sn_status sn_mcs_decide_exact(int device, int64_t num_decisions, int num_players
                               const int8_t* hand, const uint32_t* avail, int mc_per_card, int mc_max,
                               uint32_t* mt_keys, int32_t* mt_pos, int32_t* actions, int32_t* sums, int32_t* counts,
                               void* stream);
+
+/* The Philox league search (the stream law at sn_league_step) for D
+   independent decisions, one wave each: the device function the league's
+   search kernel runs, for tests.  num_players K in 2..6; board, hand, avail,
+   actions, sums, counts as sn_mcs_decide_exact; keys [D][2] uint32 = a
+   decision's Philox key, streams [D] uint64 = its stream word with j = 0
+   (playout j draws from streams[d] | j << 8); mc_max <= 1 << 20.
+   actions[d] = the card, -(card)-2 under quirk Q6, the card of a one-card
+   hand (no search, sums / counts 0), or -1 with zeroed sums / counts where
+   the hand is empty or the memory does not hold (K - 1) n <= A <= 104 cards;
+   the other decisions of the launch are not affected. */
+sn_status sn_mcs_decide_philox(int device, int64_t num_decisions, int num_players, const int8_t* board,
+                               const int8_t* hand, const uint32_t* avail, int mc_per_card, int mc_max,
+                               const uint32_t* keys, const uint64_t* streams, int32_t* actions, int32_t* sums,
+                               int32_t* counts, void* stream);
 
 /* ---- "Alpha0.5" PUCT search, PUCTAgent / PolicyMCSAgent (mcts.py:191-323) ----
    The rollouts of one decision are a dependent chain (each root choice reads

@@ -7,11 +7,13 @@
 // mix of agents, seats in seat order as GameSession.play_game calls them
 // (play.py:38-41):
 //   * DrunkHamster (agents/random.py:9): legal[random_interval(n-1)] on the
-//     slot's numpy MT19937 stream;
-//   * MCSAgent (agents/mcts.py:43-188): card memory + the reference-exact
-//     search (sechs_mcs.h) on the same stream -- so a league of DrunkHamster
-//     and MCSAgent seats replays the reference's seeded Tournament draw for
-//     draw (golden F11 "dropin" leagues);
+//     slot's stream (numpy MT19937 or Philox);
+//   * MCSAgent (agents/mcts.py:43-188): card memory + the search.  On a numpy
+//     handle the reference-exact one (sechs_mcs.h) on the slot's stream -- so
+//     a league of DrunkHamster and MCSAgent seats replays the reference's
+//     seeded Tournament draw for draw (golden F11 "dropin" leagues); on a
+//     Philox handle one lane per playout, every playout on a stream of its
+//     own (sechs_mcs_philox.h): the reference's search in law;
 //   * external agents (the net agents: PUCTAgent, PUCTCustomedAgent,
 //     BatchedACERAgent): their batched engines chose the card beforehand
 //     (sechs_puct.hip / sechs_agents.hip over the handle's decision lists); it is checked
@@ -21,6 +23,7 @@
 // Tournament.play_game, tournament.py:132-138), so the roster may change
 // between games (Tournament.evolve).
 #include "sechs_mcs.h"
+#include "sechs_mcs_philox.h"
 #include "sechs_mcs_wave.h"
 
 using namespace sechs;
@@ -50,8 +53,15 @@ __device__ __forceinline__ uint32_t league_mcs(int k, MtGen& gen, ByteBuf& buf, 
     }
 }
 
-template <int N>
+// lpf[g], set by the step's search kernel and cleared here: kLpfAll (k_league_mcs, numpy) = lpc holds every
+// non-external seat's card and the slot's stream has moved past the step; kLpfMcs (k_league_mcs_philox) = lpc
+// holds the MCS seats' cards only, the DrunkHamster seats still draw here; kLpfQ6 = quirk Q6 in a search.
+constexpr int32_t kLpfAll = 1, kLpfQ6 = 2, kLpfMcs = 4;
+
+// MODE = RNG_NUMPY_MT or RNG_PHILOX.  On Philox the kernel never searches: an MCS seat's card comes from lpc.
+template <int N, int MODE>
 __global__ __launch_bounds__(kBlock) void k_league_step(DevState s, LeagueStepArgs a) {
+    constexpr bool PH = MODE == RNG_PHILOX;
     __shared__ __attribute__((aligned(16))) uint8_t lds[kBlock * kDealStride];
     const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= s.B) return;
@@ -80,7 +90,7 @@ __global__ __launch_bounds__(kBlock) void k_league_step(DevState s, LeagueStepAr
     const int32_t pf = s.lpf ? s.lpf[g] : 0;
     if (pf) s.lpf[g] = 0;
     if (bad >= 0) return;
-    if (pf) {  // k_league_mcs drew this slot's step: its non-external seats' cards
+    if (!PH && pf) {  // k_league_mcs drew this slot's step: its non-external seats' cards
 #pragma unroll
         for (int p = 0; p < N; p++) {
             if ((uint32_t)p >= k) continue;
@@ -89,14 +99,14 @@ __global__ __launch_bounds__(kBlock) void k_league_step(DevState s, LeagueStepAr
             idx[p] = (uint32_t)max(hand_find(G.hand[p], (uint32_t)s.lpc[g * N + p]), 0);
         }
     }
-    MtGen gen;
+    typename RngOf<MODE>::T gen;
     ByteBuf buf;
-    if (!pf) RngOf<RNG_NUMPY_MT>::load(s, g, gen, buf);
+    if (PH || !pf) RngOf<MODE>::load(s, g, gen, buf);
     int32_t status = (pf >> 1) & 1;
 #pragma unroll
     for (int p = 0; p < N; p++) {  // GameSession.play_game: agents in seat order (play.py:38-41)
         if ((uint32_t)p >= k) continue;
-        if (pf) {
+        if (!PH && pf) {
             card[p] = hand_get(G.hand[p], idx[p]);
             continue;
         }
@@ -105,17 +115,22 @@ __global__ __launch_bounds__(kBlock) void k_league_step(DevState s, LeagueStepAr
         if (kind == SN_AGENT_RANDOM) {
             idx[p] = rng_interval(gen, buf, G.n - 1u);
         } else if (kind == SN_AGENT_MCS) {
-            const int64_t dn = g * N + p;
-            u32x4 mem = {s.lmem[dn], s.lmem[DN + dn], s.lmem[2 * DN + dn], s.lmem[3 * DN + dn]};
-            mem = memorize(mem, G.n, (uint32_t)kMaxCards, G.hand[p], G.b);  // mcts.py:47-49, 62-73
-            s.lmem[dn] = mem.x, s.lmem[DN + dn] = mem.y, s.lmem[2 * DN + dn] = mem.z, s.lmem[3 * DN + dn] = mem.w;
-            if (G.n == 1u) {
-                idx[p] = 0u;  // mcts.py:52-53: the last card, no search
+            if constexpr (PH) {
+                // the last card is played without a search (mcts.py:52-53); else k_league_mcs_philox chose
+                idx[p] = (G.n == 1u) ? 0u : (uint32_t)max(hand_find(G.hand[p], (uint32_t)s.lpc[g * N + p]), 0);
             } else {
-                bool q6 = false;
-                const uint32_t c = league_mcs((int)k, gen, buf, mine, G.b, G.hand[p], G.n, mem, a.mpc[agent], a.mmax[agent], &q6);
-                if (q6) status |= 1;
-                idx[p] = (uint32_t)hand_find(G.hand[p], c);
+                const int64_t dn = g * N + p;
+                u32x4 mem = {s.lmem[dn], s.lmem[DN + dn], s.lmem[2 * DN + dn], s.lmem[3 * DN + dn]};
+                mem = memorize(mem, G.n, (uint32_t)kMaxCards, G.hand[p], G.b);  // mcts.py:47-49, 62-73
+                s.lmem[dn] = mem.x, s.lmem[DN + dn] = mem.y, s.lmem[2 * DN + dn] = mem.z, s.lmem[3 * DN + dn] = mem.w;
+                if (G.n == 1u) {
+                    idx[p] = 0u;  // mcts.py:52-53: the last card, no search
+                } else {
+                    bool q6 = false;
+                    const uint32_t c = league_mcs((int)k, gen, buf, mine, G.b, G.hand[p], G.n, mem, a.mpc[agent], a.mmax[agent], &q6);
+                    if (q6) status |= 1;
+                    idx[p] = (uint32_t)hand_find(G.hand[p], c);
+                }
             }
         }
         card[p] = hand_get(G.hand[p], idx[p]);
@@ -148,7 +163,7 @@ __global__ __launch_bounds__(kBlock) void k_league_step(DevState s, LeagueStepAr
     }
     if (a.status) a.status[g] |= status;
     store_game<N>(s, g, G);
-    if (!pf) RngOf<RNG_NUMPY_MT>::store(s, g, gen, buf);
+    if (PH || !pf) RngOf<MODE>::store(s, g, gen, buf);
 }
 
 // One wave per slot whose game seats an MCSAgent this step (n >= 2): the
@@ -202,7 +217,47 @@ __global__ __launch_bounds__(64) void k_league_mcs(DevState s, LeagueStepArgs a)
         if (lane == 0u) s.lpc[g * N + p] = (int32_t)card;
     }
     wmt_store(m, s.mt + g * kMtN, s.mt_pos + g, s.mt0 + g * kMt0Levels, lane);
-    if (lane == 0u) s.lpf[g] = 1 | (q6s << 1);
+    if (lane == 0u) s.lpf[g] = kLpfAll | (q6s ? kLpfQ6 : 0);
+}
+
+// Philox handles: one wave per deciding MCS seat, lanes = playouts (sechs_mcs_philox.h).  One launch per player
+// count K the league draws (grid = B x K one-wave workgroups: seat p < K of slot g; those of a slot whose game
+// seats another count, and the seats of other agents, leave at once).  A single kernel that dispatched on the
+// slot's k shared one register allocation among the five playout loops: 211 VGPRs and 144 B of scratch against
+// the ~100 VGPRs and no scratch of each alone.  The key mixes in the slot's main counter as it
+// stands when the step begins -- k_league_step, which draws the DrunkHamster seats and moves it, runs behind these
+// kernels -- so the searches need no state of their own.  Lane 0 stores the card memory, the card (lpc) and the
+// flag (lpf).
+template <int K>
+__global__ __launch_bounds__(64) void k_league_mcs_philox(DevState s, LeagueStepArgs a) {
+    __shared__ McsPhiloxLds L;
+    const int N = s.N;
+    const int64_t g = blockIdx.x / K;
+    const uint32_t p = (uint32_t)(blockIdx.x - g * K), lane = threadIdx.x;
+    const uint32_t lg = s.lgs[g];
+    if ((lg & 15u) != (uint32_t)K) return;  // the playouts seat the game's k players (mcts.py:62-64)
+    const uint32_t agent = (lg >> (4 + 4 * p)) & 15u;
+    if (((a.kinds >> (4 * agent)) & 15u) != (uint64_t)SN_AGENT_MCS) return;
+    const Hand hp = load_hand(s, (int)p, g);
+    const uint32_t n = hand_len(hp);
+    if (n < 2u) return;  // the last card: no search (mcts.py:52-53), k_league_step plays it
+    const Board b = load_board(s, g);
+    const int64_t DN = s.B * N, dn = g * N + p;
+    u32x4 mem = {s.lmem[dn], s.lmem[DN + dn], s.lmem[2 * DN + dn], s.lmem[3 * DN + dn]};
+    mem = memorize(mem, n, (uint32_t)kMaxCards, hp, b);  // mcts.py:47-49, 62-73
+    if (lane == 0u) s.lmem[dn] = mem.x, s.lmem[DN + dn] = mem.y, s.lmem[2 * DN + dn] = mem.z, s.lmem[3 * DN + dn] = mem.w;
+    uint32_t key0, key1;
+    mcs_philox_key(s.seed, s.ctr[g], key0, key1);
+    const uint64_t stream0 = mcs_philox_stream(s.game_offset + (uint64_t)g, p, n);
+    const int mpc = a.mpc[agent], mmax = a.mmax[agent];
+    int32_t sum[kHand], cnt[kHand];
+    bool q6 = false;
+    uint32_t card = mcs_decide_philox<K>(L, b, hp, n, mem, mpc, mmax, key0, key1, stream0, lane, sum, cnt, &q6);
+    if (card == kMcsNoDeal) card = hand_get(hp, 0u);  // a memory no game leaves behind (a foreign snapshot): the lowest card
+    if (lane == 0u) {
+        s.lpc[dn] = (int32_t)card;
+        atomicOr(&s.lpf[g], kLpfMcs | (q6 ? kLpfQ6 : 0));  // one wave per MCS seat of the slot
+    }
 }
 
 // ============================================================================
@@ -220,12 +275,12 @@ sn_status sn_league_agents(sn_env* e, const int32_t* kinds, const int32_t* mc_pe
         const int mpc = mc_per_card ? mc_per_card[i] : 10, mmax = mc_max ? mc_max[i] : 100;
         if (kinds[i] == SN_AGENT_MCS) {
             if (mpc < 0 || mmax < 0) return set_error(SN_EINVAL, "mc_per_card and mc_max must be >= 0");
+            if (s.rng_mode != SN_RNG_NUMPY_MT && mmax > kMcsPhiloxMaxPlayouts)  // the playouts' stream words number them in 20 bits
+                return set_error(SN_EINVAL, "mc_max > 1 << 20 on a Philox handle");
             mcs = true;
         }
         e->lg_kind[i] = kinds[i], e->lg_mpc[i] = mpc, e->lg_mmax[i] = mmax;
     }
-    if (mcs && s.rng_mode != SN_RNG_NUMPY_MT)
-        return set_error(SN_EINVAL, "MCSAgent seats draw from numpy MT19937 streams (rng_mode numpy)");
     if (mcs && !s.lmem) {  // card memory [4][B*N], then k_league_mcs's cards [B*N] and flags [B]
         HIP_TRY(hipSetDevice(e->device));
         const size_t BN = (size_t)s.B * s.N, bytes = sizeof(uint32_t) * (5 * BN + (size_t)s.B);
@@ -242,7 +297,6 @@ sn_status sn_league_step(sn_env* e, const int32_t* actions, int32_t* rewards, in
     if (!e) return set_error(SN_EINVAL, "env is NULL");
     DevState& s = e->s;
     if (!s.lg_K) return set_error(SN_EINVAL, "not a tournament handle (sn_league_config)");
-    if (s.rng_mode != SN_RNG_NUMPY_MT) return set_error(SN_EUNSUPPORTED, "sn_league_step plays numpy-MT tournament handles");
     if (e->lg_phase < 0) return set_error(SN_EINVAL, "start the slots' games with sn_reset (seat draw + deal)");
     if (s.N < 2 || s.N > kLeagueMaxPlayers) return set_error(SN_EINVAL, "tournament handles seat 2..6 players");
     bool ext = false, mcs = false;
@@ -256,9 +310,36 @@ sn_status sn_league_step(sn_env* e, const int32_t* actions, int32_t* rewards, in
     if (ext && !actions) return set_error(SN_EINVAL, "the league has external agents: actions must be given");
     if (mcs && !s.lmem) return set_error(SN_EINVAL, "sn_league_agents did not allocate the MCS card memory");
     hipStream_t st = (hipStream_t)stream;
-    if (sn_pipe_sync(e, st) != SN_OK) return SN_EHIP;  // the step draws from the plain MT state
     a.actions = actions, a.rewards = rewards, a.played = played, a.records = records, a.invalid = invalid;
     a.status = status;
+    if (s.rng_mode != SN_RNG_NUMPY_MT) {  // Philox: no pipeline to leave; the searches, then the step
+        if (mcs && kHand - e->lg_phase >= 2) {  // one wave per deciding MCS seat, one launch per player count
+            if (s.B * s.N > 0x7FFFFFFF) return set_error(SN_EINVAL, "too many seats for one launch");
+            for (int K = s.lg_lo; K <= s.lg_hi; K++) {  // 2 <= lg_lo <= lg_hi <= 6 (sn_league_config)
+                const dim3 grid((unsigned)(s.B * K));
+                switch (K) {
+                    case 2: hipLaunchKernelGGL((k_league_mcs_philox<2>), grid, dim3(64), 0, st, s, a); break;
+                    case 3: hipLaunchKernelGGL((k_league_mcs_philox<3>), grid, dim3(64), 0, st, s, a); break;
+                    case 4: hipLaunchKernelGGL((k_league_mcs_philox<4>), grid, dim3(64), 0, st, s, a); break;
+                    case 5: hipLaunchKernelGGL((k_league_mcs_philox<5>), grid, dim3(64), 0, st, s, a); break;
+                    default: hipLaunchKernelGGL((k_league_mcs_philox<6>), grid, dim3(64), 0, st, s, a); break;
+                }
+            }
+            HIP_TRY(hipGetLastError());
+        }
+        switch (s.N) {
+            case 2: hipLaunchKernelGGL((k_league_step<2, RNG_PHILOX>), dim3(grid_for(s.B)), dim3(kBlock), 0, st, s, a); break;
+            case 3: hipLaunchKernelGGL((k_league_step<3, RNG_PHILOX>), dim3(grid_for(s.B)), dim3(kBlock), 0, st, s, a); break;
+            case 4: hipLaunchKernelGGL((k_league_step<4, RNG_PHILOX>), dim3(grid_for(s.B)), dim3(kBlock), 0, st, s, a); break;
+            case 5: hipLaunchKernelGGL((k_league_step<5, RNG_PHILOX>), dim3(grid_for(s.B)), dim3(kBlock), 0, st, s, a); break;
+            default: hipLaunchKernelGGL((k_league_step<6, RNG_PHILOX>), dim3(grid_for(s.B)), dim3(kBlock), 0, st, s, a); break;
+        }
+        HIP_TRY(hipGetLastError());
+        e->lg_phase = (e->lg_phase + 1 == kHand) ? -1 : e->lg_phase + 1;
+        e->phase = -1;
+        return SN_OK;
+    }
+    if (sn_pipe_sync(e, st) != SN_OK) return SN_EHIP;  // the step draws from the plain MT state
     if (mcs && kHand - e->lg_phase >= 2) {  // the MCS seats' searches, one wave per slot
         switch (s.N) {
             case 2: hipLaunchKernelGGL((k_league_mcs<2>), dim3((unsigned)s.B), dim3(64), 0, st, s, a); break;
@@ -270,11 +351,11 @@ sn_status sn_league_step(sn_env* e, const int32_t* actions, int32_t* rewards, in
         HIP_TRY(hipGetLastError());
     }
     switch (s.N) {
-        case 2: hipLaunchKernelGGL((k_league_step<2>), dim3(grid_for(s.B)), dim3(kBlock), 0, st, s, a); break;
-        case 3: hipLaunchKernelGGL((k_league_step<3>), dim3(grid_for(s.B)), dim3(kBlock), 0, st, s, a); break;
-        case 4: hipLaunchKernelGGL((k_league_step<4>), dim3(grid_for(s.B)), dim3(kBlock), 0, st, s, a); break;
-        case 5: hipLaunchKernelGGL((k_league_step<5>), dim3(grid_for(s.B)), dim3(kBlock), 0, st, s, a); break;
-        default: hipLaunchKernelGGL((k_league_step<6>), dim3(grid_for(s.B)), dim3(kBlock), 0, st, s, a); break;
+        case 2: hipLaunchKernelGGL((k_league_step<2, RNG_NUMPY_MT>), dim3(grid_for(s.B)), dim3(kBlock), 0, st, s, a); break;
+        case 3: hipLaunchKernelGGL((k_league_step<3, RNG_NUMPY_MT>), dim3(grid_for(s.B)), dim3(kBlock), 0, st, s, a); break;
+        case 4: hipLaunchKernelGGL((k_league_step<4, RNG_NUMPY_MT>), dim3(grid_for(s.B)), dim3(kBlock), 0, st, s, a); break;
+        case 5: hipLaunchKernelGGL((k_league_step<5, RNG_NUMPY_MT>), dim3(grid_for(s.B)), dim3(kBlock), 0, st, s, a); break;
+        default: hipLaunchKernelGGL((k_league_step<6, RNG_NUMPY_MT>), dim3(grid_for(s.B)), dim3(kBlock), 0, st, s, a); break;
     }
     HIP_TRY(hipGetLastError());
     e->lg_phase = (e->lg_phase + 1 == kHand) ? -1 : e->lg_phase + 1;  // games over: the next ones start at sn_reset

@@ -14,6 +14,7 @@
 //    MCSAgent (numpy global state bridged in and out) and by a whole-game
 //    kernel that replays GameSession(MCSAgent / DrunkHamster seats).
 #include "sechs_mcs.h"
+#include "sechs_mcs_philox.h"
 #include "sechs_mcs_wave.h"
 
 using namespace sechs;
@@ -281,10 +282,83 @@ __global__ __launch_bounds__(64) void k_mcs_decide_wave(DecideArgs a) {
     }
 }
 
+struct DecidePhiloxArgs {
+    const int8_t* board;    // [D][4][6]
+    const int8_t* hand;     // [D][10]
+    const uint32_t* avail;  // [D][4]
+    int mc_per_card, mc_max;
+    const uint32_t* keys;     // [D][2]
+    const uint64_t* streams;  // [D] stream word of playout 0
+    int32_t* actions;         // [D]
+    int32_t* sums;            // [D][10] (optional)
+    int32_t* counts;          // [D][10] (optional)
+};
+
+// The league's Philox search (mcs_decide_philox, sechs_mcs_philox.h) on given decisions, one wave
+// each (sn_mcs_decide_philox).  Every test below is uniform over the decision's one-wave workgroup.
+template <int K>
+__global__ __launch_bounds__(64) void k_mcs_decide_philox(DecidePhiloxArgs a) {
+    __shared__ McsPhiloxLds L;
+    const int64_t d = blockIdx.x;
+    const uint32_t lane = threadIdx.x;
+    u32x4 hs = {0u, 0u, 0u, 0u};
+    for (int k = 0; k < kHand; k++) {
+        const int c = a.hand[d * kHand + k];
+        if (c >= 0) hs = set_bit(hs, (uint32_t)c);
+    }
+    const Hand me = hand_from_set(hs);
+    const uint32_t n = hand_len(me);
+    const u32x4 av = {a.avail[d * 4 + 0], a.avail[d * 4 + 1], a.avail[d * 4 + 2], a.avail[d * 4 + 3]};
+    int32_t sum[kHand], cnt[kHand];
+#pragma unroll
+    for (int i = 0; i < kHand; i++) sum[i] = 0, cnt[i] = 0;
+    int32_t act = -1;  // an empty hand
+    if (n == 1u) {
+        act = (int32_t)hand_get(me, 0u);  // played without a search (mcts.py:52-53)
+    } else if (n >= 2u) {
+        bool q6 = false;
+        const uint32_t c = mcs_decide_philox<K>(L, board_from_i8(a.board + d * kRows * kThreshold), me, n, av, a.mc_per_card,
+                                                a.mc_max, a.keys[2 * d], a.keys[2 * d + 1], a.streams[d], lane, sum, cnt, &q6);
+        act = (c == kMcsNoDeal) ? -1 : q6 ? -(int32_t)c - 2 : (int32_t)c;  // -(card)-2 flags quirk Q6
+    }
+    if (lane == 0u) {
+        a.actions[d] = act;
+#pragma unroll
+        for (int i = 0; i < kHand; i++) {
+            if (a.sums) a.sums[d * kHand + i] = sum[i];
+            if (a.counts) a.counts[d * kHand + i] = cnt[i];
+        }
+    }
+}
+
 // ============================================================================
 // C ABI
 // ============================================================================
 extern "C" {
+
+sn_status sn_mcs_decide_philox(int device, int64_t D, int num_players, const int8_t* board, const int8_t* hand,
+                               const uint32_t* avail, int mc_per_card, int mc_max, const uint32_t* keys,
+                               const uint64_t* streams, int32_t* actions, int32_t* sums, int32_t* counts, void* stream) {
+    if (D <= 0 || D > 0x7FFFFFFF || !board || !hand || !avail || !keys || !streams || !actions)
+        return set_error(SN_EINVAL, "bad argument");
+    if (num_players < 2 || num_players > kLeagueMaxPlayers) return set_error(SN_EINVAL, "num_players must be in 2..6");
+    if (mc_per_card < 0 || mc_max < 0) return set_error(SN_EINVAL, "mc_per_card and mc_max must be >= 0");
+    if (mc_max > kMcsPhiloxMaxPlayouts) return set_error(SN_EINVAL, "mc_max > 1 << 20");
+    HIP_TRY(hipSetDevice(device));
+    DecidePhiloxArgs a{};
+    a.board = board, a.hand = hand, a.avail = avail, a.mc_per_card = mc_per_card, a.mc_max = mc_max;
+    a.keys = keys, a.streams = streams, a.actions = actions, a.sums = sums, a.counts = counts;
+    hipStream_t st = (hipStream_t)stream;
+    switch (num_players) {
+        case 2: hipLaunchKernelGGL((k_mcs_decide_philox<2>), dim3((unsigned)D), dim3(64), 0, st, a); break;
+        case 3: hipLaunchKernelGGL((k_mcs_decide_philox<3>), dim3((unsigned)D), dim3(64), 0, st, a); break;
+        case 4: hipLaunchKernelGGL((k_mcs_decide_philox<4>), dim3((unsigned)D), dim3(64), 0, st, a); break;
+        case 5: hipLaunchKernelGGL((k_mcs_decide_philox<5>), dim3((unsigned)D), dim3(64), 0, st, a); break;
+        default: hipLaunchKernelGGL((k_mcs_decide_philox<6>), dim3((unsigned)D), dim3(64), 0, st, a); break;
+    }
+    HIP_TRY(hipGetLastError());
+    return SN_OK;
+}
 
 sn_status sn_mcs_memorize(sn_env* e, uint32_t* avail, int mcs_num_cards, void* stream) {
     if (!e || !avail) return set_error(SN_EINVAL, "NULL argument");

@@ -56,8 +56,9 @@ struct DevState {
     uint32_t* lgs;   // [B]
     int lg_K, lg_lo, lg_hi, lg_pad;
     uint32_t* lmem;  // [4][B*N] card memory of MCSAgent seats (sn_league_step), word-major
-    int32_t* lpc;    // [B*N] cards k_league_mcs chose for the step (in lmem's allocation)
-    int32_t* lpf;    // [B] 1 (| 2: quirk Q6): lpc holds this step's non-external cards
+    int32_t* lpc;    // [B*N] cards the step's search kernel chose (in lmem's allocation)
+    int32_t* lpf;    // [B] what lpc holds for this step (kLpf*, sechs_league.hip): 1 every non-external seat's card
+                     // (k_league_mcs), 4 the MCS seats' cards only (k_league_mcs_philox); | 2: quirk Q6
 };
 
 constexpr int kMt0Levels = 16;   // word-0 crossings kept in mt0: the rounds the state array may lead the play

@@ -112,6 +112,7 @@ SIGNATURES = {
     "sn_mcs_choose": ([_P, _P, _P, _P], _I),
     "sn_mcs_play_exact": ([_P, ctypes.c_uint32, _I, _I, _P, _P, _P, _P], _I),
     "sn_mcs_decide_exact": ([_I, _I64, _I, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P], _I),
+    "sn_mcs_decide_philox": ([_I, _I64, _I, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P], _I),
     "sn_puct_root_rows": ([_P, _P, _P, _I, _P], _I),
     "sn_puct_init": ([_P, _P, _P, _P], _I),
     "sn_puct_deal": ([_P, _P, _P], _I),

@@ -20,10 +20,13 @@ host in a canonical order: game round major, then global slot id
 (`sn_elo_replay`, C++; multi_elo parity unpinned, elo.py).
 
 Agents (the pool of run.py:20-40):
-  * DrunkHamster -- drawn in-kernel from the slot's numpy stream;
-  * MCSAgent -- card memory + the reference-exact search on the slot's
-    stream (sn_league_step), so a league of DrunkHamster and MCSAgent seats
-    replays the reference's seeded Tournament bit for bit (golden F11);
+  * DrunkHamster -- drawn in-kernel from the slot's stream;
+  * MCSAgent -- card memory + the search (sn_league_step).  rng="numpy": the
+    reference-exact search on the slot's stream, so a league of DrunkHamster
+    and MCSAgent seats replays the reference's seeded Tournament bit for bit
+    (golden F11).  rng="philox": every playout draws from a Philox stream of
+    its own (the stream law in include/sechs.h at sn_league_step), one lane
+    per playout -- the reference's search in law, not draw for draw;
   * PUCTAgent / PolicyMCSAgent, PUCTCustomedAgent, BatchedACERAgent -- one
     batched engine per agent (an engine.BatchedEngine: puct.BatchedPUCT /
     BatchedPUCTCustomed, acer.BatchedACER) over the decision list of its seats in the slots'
@@ -369,8 +372,6 @@ class BatchedTournament:
         assert K >= self.max_players, "tournament.py:170: len(self) >= num_players"
         all_random = all(self.kinds[n] == KIND_RANDOM for n in self.active_agents())
         self.mode = "fused" if (self.fused and all_random) else "step"
-        if self.mode == "step" and self.rng != "numpy":
-            raise NotImplementedError("mixed leagues play numpy-MT tournament streams (rng='numpy')")
         self.env = VecSechsNimmtEnv(self.num_slots, self.max_players, seed=self.seed, game_offset=self.game_offset,
                                     rng=self.rng, device=self.device)
         self._configure()
@@ -618,7 +619,7 @@ class BatchedTournament:
         # the rank's slot offset, or the ranks' baseline lists would diverge
         shard_off = 0 if self.distributed else self.game_offset
         off = (0x40000000 + self._baseline_calls * 0x10000 + shard_off) & 0x7FFFFFFF
-        bt = BatchedTournament(evals, K, K, seed=self.seed, game_offset=off, rng="numpy", device=self.device,
+        bt = BatchedTournament(evals, K, K, seed=self.seed, game_offset=off, rng=self.rng, device=self.device,
                                net_dtype=self.net_dtype, train=False)
         seated = [self.agents[name]] + self.baseline_agents
         names = [getattr(a, "__name__", None) for a in seated]
