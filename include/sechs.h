@@ -142,8 +142,13 @@ sn_status sn_philox_counter(sn_env* env, int64_t game, uint64_t* counter_host);
    sums and count), on tournament handles the seat word and the MCS card
    memory, and the RNG in canonical form: numpy-MT as np.random.get_state()'s
    (pos, key[624]) at the play consumer's position, Philox as its 64-bit word
-   counter.  Records do not depend on the SN_OPT_* settings or on where the
-   pipelines stand, so a range of records is the state of a shard
+   counter.  A game that has drawn the last word of a round shows that
+   round's key at pos 624, as numpy does (it twists at the next draw), never
+   the next round's at pos 0; pos 0 is saved only for a state imported at
+   pos 0 and not drawn from since.  Records do not depend on the SN_OPT_* settings or on where the
+   pipelines stand (tests/test_gpu_snapshot_states.py: every record against
+   numpy's own state and the blobs of eight settings byte for byte, at every
+   stream position), so a range of records is the state of a shard
    (csrc/sechs_snapshot.h owns the layout; DESIGN.md has the table of what is
    saved and what the next launch rebuilds).
    sn_state_bytes: header + num_games records, pure host arithmetic (no GPU
@@ -166,7 +171,8 @@ sn_status sn_philox_counter(sn_env* env, int64_t game, uint64_t* counter_host);
    blob's records, blob_bytes must cover them, and blob.game_offset + first
    must equal the handle's game_offset -- every Philox stream and every
    engine draw is keyed by the global game id.  A mismatch is SN_EINVAL with
-   a message and the handle is untouched.  After a load the overrun count is
+   a message and the handle is untouched.  A record's pos above 624 is read
+   as 624 (the next draw twists).  After a load the overrun count is
    zero and the next rollout starts its pipeline from the plain state. */
 int64_t sn_state_bytes(int64_t num_games, int num_players, int rng_mode, int league, int64_t* header_bytes,
                        int64_t* record_bytes);
@@ -323,7 +329,11 @@ sn_status sn_debug_puct_phases(uint64_t* out, int n);
 /* pipeline words to the host (tests, diagnostics) [sync]: what 0 = pabsc[slot]
    (consumer positions, slots 8 and 9 = the decoder's two; B words), 1 =
    ptend[slot] (B words), 2 = decode-ahead record slot (kDecQuads x B 16-B
-   pieces, piece-major).  No pipeline state is changed. */
+   pieces, piece-major), 3 = the MT19937 state codes mt_pos[g] as they stand
+   (slot 0; B words: twist pointer | twisted-unconsumed words << 16, the form
+   a pipeline sync leaves -- read it right after a call that synchronises the
+   pipelines, such as sn_state_save, to see which conversion each game's
+   record went through).  No pipeline state is changed. */
 sn_status sn_debug_pipe_words(sn_env* env, int what, int slot, uint32_t* out);
 /* Device-side invariant checks (SN_DASSERT in sechs_env.hip and its headers:
    a played card is in its seat's hand, the cards of a step are distinct, a

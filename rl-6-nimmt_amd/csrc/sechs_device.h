@@ -499,7 +499,9 @@ __device__ __forceinline__ void rng_draws(G& gen, ByteBuf& buf, uint32_t max, ui
 // unconsumed old words [624 - (cnt - pos), 624) are untouched; the old
 // round's words [0, pos) -- all consumed -- are recoverable from the new ones
 // (the twist is invertible given the old mt[0], kept in mt0[g]), which is
-// how sn_mt_get exports such a state.
+// how sn_mt_get exports such a state.  cnt == pos < 624 (every twisted word of
+// the new round unconsumed, the old round drawn to its last word) is exported
+// the same way: numpy shows the old round at 624 (mt_code_straddles).
 //
 // Round boundary.  A lane that reaches word 624 with words of the old round
 // still buffered twists the new round's chunk 0 into registers but holds the
@@ -621,7 +623,9 @@ struct MtGenT {
     // state code for mt_pos[]; commits or drops a held-back chunk
     __device__ __forceinline__ uint32_t save(const ByteBuf& buf) {
         if (straddle) {
-            if (buf.cnt > 8u * D) return (uint32_t)kMtN | ((buf.cnt - 8u * D) << 16);  // old words left: drop
+            // old words left, or no new word drawn yet (the consumer is still
+            // in the old round, whose word 0 this path keeps nowhere else): drop
+            if (buf.cnt >= 8u * D) return (uint32_t)kMtN | ((buf.cnt - 8u * D) << 16);
             commit();
             return 8u * D | (buf.cnt << 16);
         }
@@ -685,10 +689,21 @@ using MtGen = MtGenT<1>;
 // finished the round in place when pos < 624 (mt_finish_round)
 // (a straddling code, cnt > pos, is in the previous round: its numpy key is
 // that round, restored by the caller -- sn_mt_get)
+// A consumer that has drawn a round's last word is still in that round (numpy
+// twists at the next draw: key of the round, pos 624), although the array may
+// already hold words of the next: cnt == pos counts as straddled.  The one
+// exception is the import of numpy's pos 0, code 624 | 624 << 16
+// (mt_code_from_numpy): a complete round with nothing consumed, which no
+// generator leaves by itself (MtGenT::save; k_pipe_code keeps it for a game
+// that has drawn nothing since the import).
+__host__ __device__ __forceinline__ bool mt_code_straddles(uint32_t code) {
+    const uint32_t p = code & 0x7FFu, cnt = (code >> 16) & kMtCntMask;
+    return p > 0u && (cnt > p || (cnt == p && p < (uint32_t)kMtN));
+}
 __host__ __device__ __forceinline__ int mt_numpy_pos(uint32_t code) {
     const uint32_t p = code & 0x7FFu, cnt = (code >> 16) & kMtCntMask;
     if (p == 0u) return kMtN;  // previous round complete, next draw twists
-    return (cnt > p) ? (int)(kMtN + p - cnt) : (int)(p - cnt);
+    return mt_code_straddles(code) ? (int)(kMtN + p - cnt) : (int)(p - cnt);
 }
 __host__ __device__ __forceinline__ uint32_t mt_code_from_numpy(int pos) {
     return (pos >= kMtN) ? 0u : ((uint32_t)kMtN | ((uint32_t)(kMtN - pos) << 16));

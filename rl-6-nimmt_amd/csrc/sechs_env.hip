@@ -1094,8 +1094,9 @@ static void mt_unstraddle(uint32_t* a, int T, uint32_t old0) {
 // The lazy form (sechs_device.h MtGenT: the array `key` with state code `code`, words [pos - cnt, pos) twisted and
 // unconsumed) to numpy's (key, pos), in place; old0: the newest word-0 crossing's old mt[0] (mt0).  Returns pos.
 static int32_t mt_to_numpy(uint32_t* key, uint32_t code, uint32_t old0) {
-    const int p = (int)(code & 0x7FFu), cnt = (int)((code >> 16) & kMtCntMask);
-    if (cnt > p && p > 0) mt_unstraddle(key, p, old0);  // still in the previous round, whose head [0, p) was overwritten
+    const int p = (int)(code & 0x7FFu);
+    // still in the previous round, whose head [0, p) was overwritten
+    if (mt_code_straddles(code)) mt_unstraddle(key, p, old0);
     else if (p > 0 && p < kMtN) mt_finish_round(key, p);  // twist the rest of this round in place
     return (int32_t)mt_numpy_pos(code);
 }
@@ -1281,6 +1282,8 @@ sn_status sn_debug_pipe_words(sn_env* e, int what, int slot, uint32_t* out) {
     else if (what == 1 && slot >= 0 && slot < 2) src = e->s.ptend + (int64_t)slot * B, bytes = 4 * B;
     else if (what == 2 && slot >= 0 && slot < kDecRecords && e->s.drec)
         src = e->s.drec + (int64_t)slot * kDecQuads * B, bytes = sizeof(u32x4) * kDecQuads * B;
+    else if (what == 3 && slot == 0 && e->s.mt_pos)  // as they stand: no pipeline sync
+        src = e->s.mt_pos, bytes = 4 * B;
     else return fail(SN_EINVAL, "what / slot out of range");
     HIP_TRY(hipSetDevice(e->device));
     HIP_TRY(hipDeviceSynchronize());

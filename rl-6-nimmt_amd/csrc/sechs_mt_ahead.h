@@ -460,7 +460,7 @@ __global__ __launch_bounds__(kBlock) void k_pipe_code(DevState s, int cin, int t
     // The array ran ahead of the consumer's round (whole-round twists, or
     // the K-group lead of SN_OPT_TWIST_EVERY): undo its newest round's
     // twisted words [0, tp) in place (new -> old), the host mt_unstraddle,
-    // until the unconsumed words fit one array.  With y[j] the twist's
+    // until fewer than 624 words are unconsumed (below).  With y[j] the twist's
     // intermediate (top(old[j]) | low(old[j+1])): y[j] = U(new[j] ^ X[j]),
     // X[j] = new[j-227] for j >= 227 -- all from new words, in parallel --
     // and old[j+397] for j < 227, whose y[j+396], y[j+397] the first phase
@@ -473,11 +473,22 @@ __global__ __launch_bounds__(kBlock) void k_pipe_code(DevState s, int cin, int t
     uint32_t* a = s.mt + g * kMtN;
     constexpr uint32_t D = kMtN - kMtM;
     int lvl = 0;
-    if (rem > kMtN) {
+    // Rounds are undone while a whole array or more is unconsumed (>=): a consumer exactly one array behind has
+    // drawn its round's last word and is still in that round, numpy's pos 624 -- left alone, its code
+    // 624 | 624 << 16 would read as an imported pos 0 of the round after.  The one state that IS that import
+    // stays: mt_pos still holds the code the pipeline started from (nothing writes it in between), the
+    // start-up put the consumer rem0 words before stream index 0 (k_mt_ahead INIT), so pabsc + rem0 words
+    // were drawn since; a start from 624 | 624 << 16 with none drawn keeps its last round (no mt0 level
+    // belongs to it: a load clears them, sn_mt_set leaves them stale).
+    const uint32_t code0 = s.mt_pos[g];
+    const bool at0 = code0 == ((uint32_t)kMtN | ((uint32_t)kMtN << 16)) &&
+                     s.pabsc[(int64_t)cin * s.B + g] + (uint32_t)kMtN == 0u;
+    const int32_t keep = at0 ? kMtN + 1 : kMtN;  // undo while rem >= keep
+    if (rem >= keep) {
         for (uint32_t j = lane; j < (uint32_t)kMtN; j += 64u) w[j] = a[j];
         __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
     }
-    for (; rem > kMtN && lvl < kMt0Levels; lvl++) {
+    for (; rem >= keep && lvl < kMt0Levels; lvl++) {
         SN_DASSERT(tp >= 1u && tp <= (uint32_t)kMtN);
         if (tp < 1u || tp > (uint32_t)kMtN) break;
         for (uint32_t j = D + lane; j < tp; j += 64u) y[j] = mt_untwist_y_dev(w[j] ^ w[j - D]);
@@ -504,6 +515,6 @@ __global__ __launch_bounds__(kBlock) void k_pipe_code(DevState s, int cin, int t
             s.mt0[g * kMt0Levels + lane] = v;
         }
     }
-    SN_DASSERT(rem <= kMtN);
+    SN_DASSERT(rem < keep);
     if (lane == 0u) s.mt_pos[g] = tp | ((uint32_t)max(rem, 0) << 16);
 }

@@ -56,7 +56,8 @@ __device__ __forceinline__ void snap_small_put(const DevState& s, const SnapLayo
 // One wave per game, the grid sized from B as k_pipe_code's.  MT: the 624 state words go through LDS, where the
 // lazy form (state code in mt_pos: sechs_device.h, at MtGenT) becomes numpy's:
 //   straddled (cnt > pos > 0)  the array's head [0, pos) is a round ahead of the consumer: untwisted with the
-//                              newest mt0 level, as k_pipe_code undoes a round;
+//                              newest mt0 level, as k_pipe_code undoes a round (cnt == pos < 624 too: the
+//                              consumer has drawn its round's last word, numpy shows that round at 624);
 //   mid-round (0 < pos < 624)  words [pos, 624) twisted in place, in chunks of 224 <= 227 words: word i reads
 //                              old i + 1 and old i + 397 (i < 227; neither written before this chunk ends) or
 //                              new i - 227 (written by an earlier chunk, or before pos), so a chunk's reads
@@ -87,9 +88,9 @@ __global__ __launch_bounds__(kBlock) void k_snapshot_save(DevState s, SnapHeader
         const u32x4* src = (const u32x4*)(s.mt + g * kMtN);  // 2 496 bytes per game: 16-byte aligned
         for (uint32_t q = lane; q < NV; q += 64u) *(u32x4*)(w + 4u * q) = src[q];
         const uint32_t code = s.mt_pos[g];
-        const uint32_t p = code & 0x7FFu, cnt = (code >> 16) & kMtCntMask;
+        const uint32_t p = code & 0x7FFu;
         __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-        if (cnt > p && p > 0u) {
+        if (mt_code_straddles(code)) {
             const uint32_t tp = min(p, (uint32_t)kMtN);
             for (uint32_t j = D + lane; j < tp; j += 64u) y[j] = snap_untwist_y(w[j] ^ w[j - D]);
             __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");

@@ -116,8 +116,9 @@ static_assert(kPipeSpanMax + 64 <= kPipeRing && (kPipeRing & (kPipeRing - 1)) ==
 // bound of pipe_max_chunk (592 words per two episodes at N <= 4) -- so the
 // unconsumed words are at most
 constexpr int kPipeSyncSpanMax = 296 * (2 * kTwistEveryMax + 1) + kPipeSpanMax;  // 9 351 words
-// of which one round stays twisted: the rest, in whole rounds, is undone with one mt0 level each.
-static_assert((kPipeSyncSpanMax - kMtN + kMtN - 1) / kMtN <= kMt0Levels, "mt0 holds every round k_pipe_code may undo");
+// of which fewer than 624 stay twisted: k_pipe_code undoes floor(rem / 624) rounds (while rem >= 624), 14 at most,
+// with one mt0 level each.
+static_assert(kPipeSyncSpanMax / kMtN <= kMt0Levels, "mt0 holds every round k_pipe_code may undo");
 // (Without decode-ahead the play consumer is the one followed: kPipeSpanMax at
 // most.)  One dispatch twists at most the start-up's rounds: that span, one
 // crossing per round.

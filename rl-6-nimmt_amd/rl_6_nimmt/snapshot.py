@@ -146,15 +146,19 @@ def mt_canonical_host(raw_key, code, old0=0):
     code = p | cnt << 16 (csrc/sechs_device.h, at MtGenT): words [0, p) of raw_key hold this round's values,
     [p, 624) the round's before; cnt words just before p are twisted and not consumed yet.
       p == 0 or p == 624   a complete round (code 0: np.random.seed's state, pos 624): copied;
-      0 < p < 624, cnt <= p   mid-round: words [p, 624) are twisted in place, pos = p - cnt;
+      0 < p < 624, cnt < p   mid-round: words [p, 624) are twisted in place, pos = p - cnt;
       cnt > p > 0   straddled: the consumer is still in the round before, whose head [0, p) the twist has
                     overwritten; it is untwisted (old0: the old mt[0], whose low 31 bits the twist never
-                    reads), pos = 624 + p - cnt."""
+                    reads), pos = 624 + p - cnt;
+      cnt == p < 624   straddled as well: the consumer has drawn its round's last word, and numpy, which
+                    twists at the next draw, shows that round at pos 624.  cnt == p == 624 is the import of
+                    numpy's pos 0 (mt_code_from_numpy) and stays pos 0 (mt_code_straddles, csrc/sechs_device.h)."""
     a = [int(x) for x in np.asarray(raw_key, dtype=np.uint32)]
     assert len(a) == MT_N
     p, cnt = int(code) & 0x7FF, (int(code) >> 16) & 0x3FF
     D = MT_N - MT_M
-    if cnt > p > 0:
+    straddles = p > 0 and (cnt > p or (cnt == p and p < MT_N))
+    if straddles:
         y = [0] * MT_N
         for j in range(D, p):
             y[j] = _untwist_y(a[j] ^ a[j - D])
@@ -172,5 +176,5 @@ def mt_canonical_host(raw_key, code, old0=0):
     if p == 0:
         pos = MT_N
     else:
-        pos = MT_N + p - cnt if cnt > p else p - cnt
+        pos = MT_N + p - cnt if straddles else p - cnt
     return np.array(a, dtype=np.uint32), pos

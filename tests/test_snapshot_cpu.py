@@ -105,6 +105,56 @@ def test_straddled(p, q):
     check_continues(key, pos, at(seed, q))
 
 
+@pytest.mark.parametrize("p", [8, 64, 224, 232, 400, 616])
+def test_last_word_of_a_round_drawn(p):
+    """cnt == p < 624: the consumer has drawn word 623 of round 1 and the twist has run p words into round 2.
+    numpy twists at the next draw, so get_state() is still round 1's key at pos 624 -- not round 2's at pos 0"""
+    seed = 9
+    K = rounds(seed, 2)
+    raw = np.concatenate((K[2][:p], K[1][p:]))
+    key, pos = S.mt_canonical_host(raw, p | (p << 16), old0=K[1][0])
+    assert pos == MT_N
+    check_continues(key, pos, at(seed, MT_N))
+
+
+def test_imported_pos_zero_stays_zero():
+    """code 624 | 624 << 16 is mt_code_from_numpy(0): a state set at pos 0 (numpy never shows it by itself) is a
+    complete round with nothing drawn; it is saved as it was set, and continues with the round's word 0"""
+    K = rounds(4, 1)
+    key, pos = S.mt_canonical_host(K[1], MT_N | (MT_N << 16))
+    assert pos == 0 and np.array_equal(key, K[1])
+    rs = np.random.RandomState(0)
+    rs.set_state(("MT19937", key, pos))
+    assert rs.bytes(4000) == at(4, 0).bytes(4000)  # round 1 from its word 0: what the seeded state draws first
+
+
+@pytest.mark.parametrize("n,c", [(4, 104), (2, 24), (10, 104)])
+def test_sweep_inputs_stay_wide(n, c):
+    """The inputs of tests/test_gpu_snapshot_states.py, with the oracle alone: at each of the five save points of
+    the schedule at least 100 of the 640 games stand in each of the pos bands 1-227, 228-397 and 398-623, and the
+    positions reached over the five points cover at least 600 of the 624 values 1 .. 624 (measured: the smallest
+    band count is 165, a single point already has about 400 distinct positions).  An edit of the inputs that
+    narrows the sweep fails here."""
+    import snapshot_states as X
+
+    assert (n, c) in X.SHAPES and X.B == 640 and X.CHUNKS == (1, 2, 7, 13, 17)
+    key0, pos0 = X.start_states()
+    assert sorted(set(pos0.tolist())) == list(range(625))  # the start states: every position, 0 and 624 included
+    saves, _ = X.sweep(n, c)
+    assert len(saves) == 6
+    seen, least = set(), X.B
+    for s in saves[1:]:
+        pos = s["pos"]
+        assert pos.min() >= 1 and pos.max() <= MT_N  # numpy's own range
+        for lo, hi in ((1, 227), (228, 397), (398, 623)):
+            k = int(((pos >= lo) & (pos <= hi)).sum())
+            least = min(least, k)
+            assert k >= 100, (lo, hi, k)
+        seen |= set(pos.tolist())
+    print(f"{n} players, {c} cards: smallest band count {least}, {len(seen)} distinct positions")
+    assert len(seen) >= 600
+
+
 def test_pack_unpack_round_trip():
     rng = np.random.RandomState(1)
     for mode, league in ((S.RNG_NUMPY_MT, False), (S.RNG_NUMPY_MT, True), (S.RNG_PHILOX, False), (S.RNG_PHILOX, True)):
